@@ -6,7 +6,12 @@ A step = one outer iteration of SSS_amg_solve (Solve/SSS_SOLVE.c:53-80): one V-c
 (SSS_main.c:141-145), synthetic operator generated in memory (a 400^3 .mtx would be ~60 GB of text).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 400] [--mode throughput|parity]
-                    [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run does what the headline figure needs and no more: setup, warm-up, the K timed steps, the
+optional --dump-outputs, the result line.  --full adds every other measurement to the same line: the
+level-0 SpMV roofline launches, iterations to tol and AMG-PCG, the parity-mode mirror with the
+reference-semantics ladder, the committed PMC traffic record, the CPU baselines.
 
 Modes:
   throughput : exact GS-CF on level 0 (red-black -> fully parallel), two-stage GS-CF on coarser
@@ -46,6 +51,14 @@ def parse():
                         "launches N ranks itself (torch.distributed.run) before touching the GPU")
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary measurements (level-0 SpMV roofline, "
+                        "iterations to tol, AMG-PCG, the parity-mode mirror, the CPU baselines); without it "
+                        "their fields of the result line are null and the options that tune them are unused")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last of them returned -- the level-0 iterate x "
+                        "and the residual norm -- as float64 DIR/<name>.npy (an x above the size budget as a "
+                        "fixed, seeded sample; N > 1: one x file per rank)")
     p.add_argument("--grid", "--n", dest="n", type=int, default=None,
                    help="grid edge (default 400: the metric's 64M-row problem at every rank count, so that "
                         "--gpus 1/2/4/8 form one strong-scaling curve; BASELINE.json's other configs: "
@@ -106,7 +119,10 @@ def parse():
     argv = None
     if "WORLD_SIZE" in os.environ and "SSS_BENCH_ARGV" in os.environ:   # ranks spawned by spawn_ranks()
         argv = json.loads(os.environ["SSS_BENCH_ARGV"])
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Dist:
@@ -242,6 +258,42 @@ def host_cpus() -> dict:
     return info
 
 
+def full_only_options(args) -> list:
+    """The options of this command line that tune parts only --full runs (given with a value other
+    than their default): a plain run names them on stderr instead of ignoring them silently."""
+    defaults = {"converge_max": 100, "parity_cycles": 2, "parity_converge": None, "no_cpu_baseline": False,
+                "cpu_threads": 0, "cpu_iters": 5, "cpu_warmup": 1, "cpu_n": 0}
+    return ["--" + k.replace("_", "-") for k, v in defaults.items() if getattr(args, k) != v]
+
+
+DUMP_MAX_ENTRIES = 4 * 2**20  # float64 entries of x per run, all ranks together (32 MiB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirpath, x: np.ndarray, absres: float, rank: int, world: int) -> dict:
+    """--dump-outputs: what the last timed step handed its caller -- the level-0 iterate x (this
+    rank's rows) and ||b - A0 x|| -- as float64 .npy files.  An x longer than this rank's share of
+    DUMP_MAX_ENTRIES is sampled at sorted positions drawn from a fixed seed, the same in every run
+    of that size, so that two builds can be compared entry for entry."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    cap = DUMP_MAX_ENTRIES // world
+    what = f"all {len(x)} entries"
+    if len(x) > cap:
+        # one position in each of cap equal strata of the index range: ascending without a sort
+        lo = np.arange(cap, dtype=np.int64) * len(x) // cap
+        hi = np.arange(1, cap + 1, dtype=np.int64) * len(x) // cap
+        idx = lo + np.random.default_rng(DUMP_SEED + rank).integers(0, hi - lo)
+        what = (f"{cap} of {len(x)} entries (one per equal stratum of the index range, numpy "
+                f"default_rng({DUMP_SEED + rank}).integers)")
+        x = x[idx]
+    name = "x" if world == 1 else f"x_rank{rank}"
+    np.save(d / f"{name}.npy", np.ascontiguousarray(x, dtype=np.float64))
+    if rank == 0:
+        np.save(d / "residual_norm.npy", np.array([absres], dtype=np.float64))
+    return {"dir": str(d), name: what, "residual_norm": "||b - A0 x|| after the last timed step"}
+
+
 def spawn_ranks(n: int) -> int:
     """Launch this script as n ranks under torch.distributed.run (child process; this process
     never initialises the GPU) and return its exit code."""
@@ -267,8 +319,9 @@ class Single:
         self.rows, self.ghosts = N, 0
 
     def set_ones(self):
-        self.DH.upload(0, "b", np.ones(self.N))
-        self.DH.upload(0, "x", np.ones(self.N))
+        one = np.ones(self.N)
+        self.DH.upload(0, "b", one)
+        self.DH.upload(0, "x", one)
 
     def set_x_ones(self):
         self.DH.upload(0, "x", np.ones(self.N))
@@ -482,6 +535,10 @@ def make_comm(A, D):
 
 def main():
     args = parse()
+    marks = [("start", time.perf_counter())]   # where the run's wall time goes, one stderr line at the end
+
+    def mark(name):
+        marks.append((name, time.perf_counter()))
     ws = os.environ.get("WORLD_SIZE")
     if ws is None and args.gpus is not None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))   # before anything touches the GPU
@@ -512,11 +569,19 @@ def main():
                                        "workload": workload}) + "\n").encode())
         D.close()
         return
+    if not args.full and D.rank == 0:
+        unused = full_only_options(args)
+        if unused:
+            print(f"[bench] {', '.join(unused)}: no effect without --full (the parts they tune are not run)",
+                  file=sys.stderr, flush=True)
     if args.parity_converge is None:
         args.parity_converge = 1 if D.world == 1 else 0
+    if not args.full:   # a plain run: the timed steps only
+        args.converge_max, args.parity_cycles, args.parity_converge, args.no_cpu_baseline = 0, 0, 0, True
     hb_stop = threading.Event()
     threading.Thread(target=heartbeat, args=(hb_stop, time.perf_counter()), daemon=True).start()
     import amg_amd as A
+    mark("import")
     comm, dev, transport = make_comm(A, D) if D.world > 1 else (None, 0, None)
 
     n = args.n
@@ -629,6 +694,7 @@ def main():
             shutil.rmtree(prefix.parent, ignore_errors=True)
             print(f"[bench] removed the partition set {prefix.parent}", file=sys.stderr, flush=True)
     upload_s = time.perf_counter() - t0
+    mark("operator+setup+upload")
     # HBM in use on each rank's device once its mirror is resident (ranks sharing one GPU all see
     # the device total)
     hbm_ranks = D.gather(A.hbm_used_bytes() / 1e9)
@@ -640,6 +706,7 @@ def main():
           f"{' (after the setup; the rest overlapped it)' if overlapped else ''}", file=sys.stderr, flush=True)
     eng.set_ones()
     DH = eng
+    mark("b, x0")
 
     for _ in range(args.warmup):
         DH.cycle()
@@ -649,6 +716,7 @@ def main():
     # (then eager launches; SSS_HIP_DIST_GRAPH=0 forces them)
     cycle_graph = DH.DH.level_flags(0)["cycle_graph"] if D.world > 1 else None
     D.barrier()
+    mark("warm-up")
     t0 = time.perf_counter()
     absres = 0.0
     for it in range(args.steps):
@@ -665,10 +733,16 @@ def main():
     # the stored-format bytes the timed step's kernels read and write (the next cycle as it would run
     # now -- the steady state of the loop above -- and the residual + norm; sss_hip_cycle_bytes)
     cyc_bytes = DH.DH.cycle_bytes() if D.world == 1 else None
+    mark("timed steps")
+    dumped = None
+    if args.dump_outputs:   # before anything below moves x again
+        dumped = dump_outputs(args.dump_outputs, DH.DH.download(0, "x") if D.world == 1 else DH.DH.download("x"),
+                              absres, D.rank, D.world)
+        mark("dump")
 
     # roofline of the dominant streaming kernel: level-0 fused residual SpMV (wp = b - A0 x);
     # N > 1: rank 0's share (its rows, x with ghosts), no exchange inside the timed launches
-    spmv_ms = DH.time_level0_spmv(20)   # the cycle's own storage of A_0
+    spmv_ms = DH.time_level0_spmv(20) if args.full else None   # the cycle's own storage of A_0
     a_format = None
     launches, tail_from = None, None
     level_formats = None
@@ -684,7 +758,7 @@ def main():
         # the stored format's own bytes (dictionary ELL: 8 B per row + block dictionaries) + vectors
         spmv_bytes = info0.a_stream_bytes + 8 * N + 8 * N + 8 * N
         # SURVEY.md 8(d)'s kernel: the same residual SpMV from A_0's CSR arrays
-        csr_ms = DH.DH.time_level0_spmv_csr(20)
+        csr_ms = DH.DH.time_level0_spmv_csr(20) if args.full else None
         launches = A.lib().sss_hip_cycle_launches(DH.DH.h)   # kernels per V-cycle (captured graph)
         tail_from = A.lib().sss_hip_tail_from(DH.DH.h)
     else:
@@ -694,11 +768,13 @@ def main():
         csr_ms = spmv_ms
     # roofline: SURVEY.md 8(d)'s algorithmic bytes of the CSR SpMV over the CSR kernel's time; the
     # cycle's own (compressed) storage of A_0 is reported beside it with its own bytes
-    achieved = csr_bytes / (csr_ms * 1e-3) / 1e9
-    format_gbps = spmv_bytes / (spmv_ms * 1e-3) / 1e9
+    if args.full:
+        achieved = csr_bytes / (csr_ms * 1e-3) / 1e9
+        format_gbps = spmv_bytes / (spmv_ms * 1e-3) / 1e9
 
     # iterations to tol from x0 = 1 (the CLI's problem), and time to solution
-    DH.set_x_ones()
+    if args.full:
+        DH.set_x_ones()
     sumb = float(np.sqrt(N))
     its = 0
     t0 = time.perf_counter()
@@ -766,7 +842,7 @@ def main():
         # throughput mode must converge within the reference's count + 2
         ref_conv["ladder"] = ("ok" if parity["final_relres"] < pars["tol"] and relres < pars["tol"]
                               and its <= parity["iterations_to_tol"] + 2 else "violated")
-    elif conv.exists() and args.stencil == 7 and not irregular:
+    elif args.full and conv.exists() and args.stencil == 7 and not irregular:
         try:
             cj = json.loads(conv.read_text())["modes"]
             ref_conv = {"iterations_to_tol_reference": cj["parity"]["iters"],
@@ -787,7 +863,7 @@ def main():
     # inside this process), with the commit it was measured at
     traffic, traffic_src = None, None
     pmcs = sorted((ROOT / "profiles").glob("r*_level0_spmv_pmc.json"))
-    if pmcs and D.world == 1 and not irregular:
+    if args.full and pmcs and D.world == 1 and not irregular:
         try:
             rec = json.loads(pmcs[-1].read_text())
             if rec.get("n") == n and rec.get("a_format") == a_format:
@@ -856,7 +932,7 @@ def main():
     rec = {
         "metric": "V-cycle iters/sec + fine-level SpMV GB/s (%HBM peak), 64M-row 7pt Poisson",
         "value": value, "unit": "V-cycle iter/s", "n_gpus": D.world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "full": args.full, "outputs": dumped,
         "scaling": "strong" if D.world > 1 else None, "vs_baseline": None,
         "dtype": "f64",
         "data": (f"{mtx} read by SSS_mat_read (the reference's .mtx ingest), b = x0 = 1" if mtx is not None else
@@ -876,7 +952,8 @@ def main():
                    "single_workgroup_tail_from_level": tail_from if tail_from is not None and tail_from >= 0 else None,
                    "level_smoothers": [["exact", "hybrid", "jacobi"][k] + (f"+inner{i}" if i else "")
                                        for k, i in level_smoothers] if level_smoothers else None,
-                   "iterations_to_tol": its, "final_relres": relres, "time_to_solution_s": solve_s,
+                   "iterations_to_tol": its if args.full else None, "final_relres": relres if args.full else None,
+                   "time_to_solution_s": solve_s if args.full else None,
                    "amg_pcg": pcg,
                    "reference_convergence": ref_conv,
                    "time_to_solution_reference_semantics_s": (ref_conv["iterations_to_tol_reference"] / parity["value"])
@@ -890,9 +967,9 @@ def main():
                    "hbm_used_gb_max_over_ranks": hbm_gb,
                    "hbm_used_gb_per_rank": hbm_ranks,
                    "partition_set": part_rec,
-                   "relres_history": history,
+                   "relres_history": history if args.full else None,
                    "transport": transport},
-        "roofline": {"bound": "hbm", "kernel": "spmv_adaptive<RESID> level 0 from its CSR arrays (y = b - A0 x)",
+        "roofline": ({"bound": "hbm", "kernel": "spmv_adaptive<RESID> level 0 from its CSR arrays (y = b - A0 x)",
                      "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": achieved / PEAK_HBM_GBS,
                      # the same residual as the V-cycle runs it, from its own (compressed) storage
                      "cycle_storage_frac": format_gbps / PEAK_HBM_GBS,
@@ -908,7 +985,8 @@ def main():
                          "csr_equivalent_rate_GBps": csr_bytes / (spmv_ms * 1e-3) / 1e9,
                          "note": "bytes = the stored format of A_0 (dictionary ELL: 8 B per row of codes + block "
                                  "dictionaries) + x, b, y; csr_equivalent = SURVEY 8(d) CSR bytes over this "
-                                 "kernel's time, the rate a CSR SpMV would need to match it"}},
+                                 "kernel's time, the rate a CSR SpMV would need to match it"}}
+                     if args.full else None),
         # the V-cycle's roofline: the bytes its kernels actually move in their stored formats
         "vcycle_stored": ({
             "bytes_per_step": cyc_bytes["total"], "GBps": cyc_bytes["total"] / (ms_per_step * 1e-3) / 1e9,
@@ -955,11 +1033,15 @@ def main():
         rec["speedup_parity_vs_cpu_reference_semantics_1_thread"] = parity["value"] / cpu_baseline["value"]
     if cpu_mt:
         rec["speedup_throughput_vs_cpu_same_mode_all_cores"] = value / cpu_mt["value"]
+    mark("secondary measurements" if args.full else "record")
     DH.close()
     if comm is not None:
         comm.close()
     hb_stop.set()
+    mark("close")
     if D.rank == 0:
+        print("[bench] wall: " + ", ".join(f"{name} {t - t_prev:.2f} s" for (name, t), (_, t_prev)
+                                           in zip(marks[1:], marks)), file=sys.stderr, flush=True)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(rec) + "\n").encode())
     D.close()

@@ -247,6 +247,48 @@ def test_bench_workload_flags():
     assert bench.select_workload(ns(stencil=27, n=64), 4) == (27, 64)
 
 
+def test_bench_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files; an x within the budget whole, a longer one at sorted
+    positions that depend on the length, rank and seed alone (two runs write the same entries), every
+    rank's share together within the budget."""
+    import bench
+    x = np.arange(1000, dtype=np.float64) * 0.5
+    rec = bench.dump_outputs(tmp_path / "a", x, 3.25, 0, 1)
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, x)
+    assert np.load(tmp_path / "a" / "residual_norm.npy").tolist() == [3.25]
+    assert rec["dir"] == str(tmp_path / "a") and "all 1000" in rec["x"]
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 64)
+    for d in ("b", "c"):
+        for rank in range(2):
+            bench.dump_outputs(tmp_path / d, x + rank, 1.0, rank, 2)
+    for rank in range(2):
+        s = np.load(tmp_path / "b" / f"x_rank{rank}.npy")
+        assert s.dtype == np.float64 and s.shape == (32,)
+        assert np.array_equal(s, np.load(tmp_path / "c" / f"x_rank{rank}.npy"))
+        pos = (s - rank) * 2   # x[i] = i / 2 (+ rank): the sampled positions
+        assert np.all(np.diff(pos) >= 0) and pos.min() >= 0 and pos.max() < 1000
+    assert not (tmp_path / "b" / "x.npy").exists()
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["residual_norm.npy", "x_rank0.npy", "x_rank1.npy"]
+
+
+def test_bench_options(monkeypatch):
+    """--full and --dump-outputs exist and are off by default; --steps below 1 is refused."""
+    import bench
+    monkeypatch.delenv("SSS_BENCH_ARGV", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and bench.full_only_options(a) == []
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--converge-max", "50", "--no-cpu-baseline", "--cpu-iters", "5"])
+    assert bench.full_only_options(bench.parse()) == ["--converge-max", "--no-cpu-baseline"]
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_bench_transport_policy_fails_loudly_on_distinct_gpus():
     """RCCL failing when every rank owns a GPU is a fault, not a reason to fall back to the host
     transport; the fallback is only for ranks sharing GPUs (the one-GPU test box)."""

@@ -70,3 +70,43 @@ def test_cycle_bytes_no_side_effects_and_bounds(kind, n, mode):
         nc = H.level(nl - 1).A.num_rows
         assert cb["coarse"] >= 8 * nc * nc
     D.close()
+
+
+def test_bench_plain_run_line_and_dump(tmp_path):
+    """A plain `bench.py` run (no --full) end to end at 32^3: the headline fields, the secondary
+    measurements null and not run, an option of theirs named on stderr, and --dump-outputs = the
+    level-0 iterate and the residual norm of the last timed step.  The two dumped files must belong
+    together: ||b - A0 x|| recomputed on the host from x.npy equals residual_norm.npy to float64
+    rounding.  Bound: each residual entry carries at most ~8 * 2^-53 * sum|a_ij x_j| <= 1e-15 * 12 max|x|,
+    over 32768 entries that is below 3e-12 * max|x| in the norm, and the sum of squares adds a relative
+    n * 2^-53 = 4e-12 (1e-9 asked)."""
+    import json
+    import subprocess
+
+    import amg_amd as A
+
+    n = 32
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--n", str(n), "--steps", "2",
+                        "--warmup", "1", "--converge-max", "50", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=300, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["full"] is False and rec["steps"] == 2 and rec["warmup"] == 1 and rec["dtype"] == "f64"
+    assert rec["unit"] == "V-cycle iter/s" and rec["higher_is_better"] is True
+    assert rec["value"] > 0 and abs(rec["ms_per_step"] * rec["value"] - 1e3) < 1e-6 * 1e3
+    for k in ("roofline", "parity_mode", "cpu_baseline", "cpu_baseline_same_mode"):
+        assert rec[k] is None, k
+    cfg = rec["config"]
+    assert cfg["rows"] == n ** 3 and cfg["iterations_to_tol"] is None and cfg["amg_pcg"] is None
+    assert cfg["reference_convergence"] is None and cfg["relres_history"] is None
+    assert rec["vcycle_stored"]["bytes_per_step"] > 0
+    assert "converge iteration" not in r.stderr and "CPU baseline" not in r.stderr
+    assert "--converge-max: no effect without --full" in r.stderr
+    x = np.load(tmp_path / "d" / "x.npy")
+    nrm = np.load(tmp_path / "d" / "residual_norm.npy")
+    assert x.dtype == np.float64 and x.shape == (n ** 3,) and nrm.dtype == np.float64 and nrm.shape == (1,)
+    assert rec["outputs"]["dir"] == str(tmp_path / "d") and "all 32768" in rec["outputs"]["x"]
+    rp, ci, v = A.csr_arrays(A.generate(7, n))
+    res = np.ones(n ** 3) - np.add.reduceat(v * x[ci], rp[:-1])
+    assert np.isfinite(x).all() and nrm[0] > 0
+    assert abs(float(np.sqrt(np.dot(res, res))) - nrm[0]) <= 1e-9 * nrm[0] + 3e-12 * np.abs(x).max()

@@ -15,7 +15,7 @@ Per file:
   ladder), that count measured by the parity engine on the same operator;
 - the drop-in CLI (amg file.mtx, the reference's main): the printed relres column equals the oracle's
   history at %13.6e on small inputs;
-- bench.py --mtx: one GPU run of the bench line on the file (small inputs).
+- bench.py --full --mtx: one GPU run of the whole bench line on the file (small inputs).
 """
 from __future__ import annotations
 
@@ -109,7 +109,7 @@ def test_bench_mtx_line(mtx):
     if H.level(0).A.num_rows > SMALL:
         pytest.skip("the full bench line on large files is a bench run, not a test")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--mtx", str(p), "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads(r.stdout.strip().splitlines()[-1])
     assert rec["config"]["workload"] == f"mtx_{p.stem}"

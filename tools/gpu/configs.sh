@@ -1,7 +1,7 @@
 # the other BASELINE workloads on one GPU: G3_circuit stand-in, 27-pt anisotropic 256^3
-cd "$GRAFT_REPO_ROOT" || exit 1
-mkdir -p gpurun_out
-timeout -k 10 600 python -u bench.py --workload circuit --no-cpu-baseline > gpurun_out/bench_circuit.json 2> gpurun_out/bench_circuit.err || { tail -20 gpurun_out/bench_circuit.err; exit 1; }
-head -c 300 gpurun_out/bench_circuit.json; echo
-timeout -k 10 900 python -u bench.py --stencil 27 --n 256 --no-cpu-baseline --parity-cycles 0 > gpurun_out/bench_a27.json 2> gpurun_out/bench_a27.err || { tail -20 gpurun_out/bench_a27.err; exit 1; }
-head -c 300 gpurun_out/bench_a27.json
+cd "$(dirname "$0")/../.." || exit 1
+export OUT=${OUT:-out}; mkdir -p $OUT
+timeout -k 10 600 python -u bench.py --full --workload circuit --no-cpu-baseline > $OUT/bench_circuit.json 2> $OUT/bench_circuit.err || { tail -20 $OUT/bench_circuit.err; exit 1; }
+head -c 300 $OUT/bench_circuit.json; echo
+timeout -k 10 900 python -u bench.py --full --stencil 27 --n 256 --no-cpu-baseline --parity-cycles 0 > $OUT/bench_a27.json 2> $OUT/bench_a27.err || { tail -20 $OUT/bench_a27.err; exit 1; }
+head -c 300 $OUT/bench_a27.json
