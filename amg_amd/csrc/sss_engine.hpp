@@ -259,6 +259,7 @@ struct DevCSR {
     int mg_G = 0;              // 0: no merged copy
     int mg_ng = 0;             // groups
     int mg_W = 4;              // waves per group (1, 2 or 4): 4 / mg_W groups per workgroup
+    int mg_acc = 0;            // lane accumulators of the merged kernels: 0 registers, 1 LDS (SSS_HIP_MERGE_ACC)
     int *mg_gp = nullptr;      // per group: first entry (mg_ng + 1)
     bool mg_two = false;       // two-segment rows
     unsigned *mg_k = nullptr;

@@ -887,7 +887,8 @@ __global__ __launch_bounds__(kBlock) void relax_range_wave(int lo, int hi, const
 // ---- two-stage GS-CF (oracle: ora_cf_twostage) ----------------------------------------------
 // Stage 0 over the reordered pass rows [N_i | L_i] (local row q = global lo + q):
 //   P_q = b - sum_{N_i} a x;  y_q = (P_q - sum_{L_i} a x) / d   (x from before the pass)
-template <int PATH>   // 0 tile, 1 wave chain, 2 wave tree (free order)
+// (LDSACC: merged groups with the lanes' accumulators in LDS, DevCSR::mg_acc)
+template <int PATH, bool LDSACC = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
 __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int *__restrict__ split,
                                                     const double *__restrict__ b, XSrc x,
                                                     const double *__restrict__ deff, double *__restrict__ P,
@@ -934,10 +935,11 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
     } else if constexpr (PATH >= 3) {   // merged row groups, G = PATH, M.mg_W waves per group
         constexpr int G = PATH;
         __shared__ double red[8 * G];
+        __shared__ double acc[LDSACC ? 4 * 2 * G * kMergeAccDoubles : 1];
         int g = 0, u = 0;
         double n_sum = 0.0, l_sum = 0.0;
-        if (merged_block<G, 2>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, [&](int c) -> double { return x(c); }, red, g, u,
-                               n_sum, l_sum)) {
+        if (merged_block<G, 2, LDSACC>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, [&](int c) -> double { return x(c); },
+                                       red, acc, g, u, n_sum, l_sum)) {
             const int q = g * G + u;
             if (q < M.n) {
                 const double Pq = b[lo + q] - n_sum;
@@ -1025,7 +1027,7 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
 
 // Inner step over the L-only rows:  y_q = (P_q - sum_{L_i} a yp[j - lo]) / d  (keeps yp_q if |d| small)
 // (column c reads ycols[c - col_off]; a row with |d| small keeps ykeep[q]; rows are lo + q)
-template <int PATH>   // 0 tile, 1 wave chain, 2 wave tree (free order)
+template <int PATH, bool LDSACC = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
 __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const double *__restrict__ deff,
                                                    const double *__restrict__ P, const double *ycols, int col_off,
                                                    const double *ykeep, double *__restrict__ y)
@@ -1067,10 +1069,11 @@ __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const doubl
     } else if constexpr (PATH >= 3) {   // merged row groups, G = PATH, M.mg_W waves per group
         constexpr int G = PATH;
         __shared__ double red[8 * G];
+        __shared__ double acc[LDSACC ? 4 * G * kMergeAccDoubles : 1];
         int g = 0, u = 0;
         double l_sum = 0.0, unused = 0.0;
-        if (merged_block<G, 1>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, fetch,
-                               red, g, u, l_sum, unused)) {
+        if (merged_block<G, 1, LDSACC>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, fetch, red, acc, g, u, l_sum,
+                                       unused)) {
             const int q = g * G + u;
             if (q < M.n) finish(q, P[q] - l_sum);
         }
@@ -1138,8 +1141,12 @@ void launch_ts_stage0(const DevCSR &M, int lo, const int *split, const double *b
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + x gathers, b, deff, P and y
-    if (M.mg_G == 8 && M.mg_two)
+    if (M.mg_G == 8 && M.mg_two && M.mg_acc)
+        hipLaunchKernelGGL((ts_stage0<8, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
+    else if (M.mg_G == 8 && M.mg_two)
         hipLaunchKernelGGL(ts_stage0<8>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
+    else if (M.mg_G == 4 && M.mg_two && M.mg_acc)
+        hipLaunchKernelGGL((ts_stage0<4, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
     else if (M.mg_G == 4 && M.mg_two)
         hipLaunchKernelGGL(ts_stage0<4>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
     else if (M.vec_rows)
@@ -1161,8 +1168,14 @@ void launch_ts_inner(const DevCSR &M, int lo, const double *deff, const double *
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + y gathers, deff, P, ykeep and y
-    if (M.mg_G == 8)
+    if (M.mg_G == 8 && M.mg_acc)
+        hipLaunchKernelGGL((ts_inner<8, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off,
+                           ykeep, y);
+    else if (M.mg_G == 8)
         hipLaunchKernelGGL(ts_inner<8>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
+    else if (M.mg_G == 4 && M.mg_acc)
+        hipLaunchKernelGGL((ts_inner<4, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off,
+                           ykeep, y);
     else if (M.mg_G == 4)
         hipLaunchKernelGGL(ts_inner<4>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
     else if (M.vec_rows)

@@ -819,6 +819,25 @@ static bool xell_on()
     return !(e && *e == '0');
 }
 
+// Where the lanes of the merged-group kernels keep their accumulators (DevCSR::mg_acc): 0 registers,
+// 1 LDS (merged_sums_lds).  SSS_HIP_MERGE_ACC forces one form (read per upload: tests compare both
+// ways); unset, the default per (G, two segments).  LDS for every pair the cycle selects, measured
+// on 7-pt 400^3 against the previous commit's library (profiles/merged_acc/prof_shapes_*.txt, kernel
+// time summed over the six traced cycles): G = 4 two segments (ts_stage0<4>) 22.39 -> 20.75 ms over
+// its 12 launch shapes, G = 4 one segment (ts_inner<4>, spmv_merged<.,.,4>) 8.60 -> 8.03 ms, G = 8
+// one segment (spmv_merged<.,.,8>) 2.31 -> 2.17 ms.  Two shapes of ts_stage0<4> with the shortest
+// per-wave shares (~180 entries: 17,164 and 25,478 workgroups) are 2-4 % slower in LDS, the ten
+// others 5-24 % faster.
+// G = 8 with two segments is instantiated but never selected (devcsr_upload caps those at G = 4);
+// its LDS form holds 32.5 KB per workgroup, 4 waves per SIMD against the register form's 5.
+static int merge_acc(int G, bool two)
+{
+    const char *e = getenv("SSS_HIP_MERGE_ACC");
+    if (e && *e) return *e != '0';
+    (void)G, (void)two;
+    return 1;
+}
+
 int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *seg)
 {
     PhaseTimer pt("devcsr");
@@ -872,6 +891,7 @@ int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *se
         const char *wz = getenv("SSS_HIP_MERGE_W");
         d.mg_W = (wz && *wz) ? atoi(wz) : 4;
         d.mg_W = d.mg_W >= 4 ? 4 : d.mg_W >= 2 ? 2 : 1;
+        d.mg_acc = merge_acc(d.mg_G, d.mg_two);
         if (int rc = merged_build_device(d, seg)) return rc;
         d.ngrid = (d.mg_ng + 4 / d.mg_W - 1) / (4 / d.mg_W);
     } else if (d.mg_G > 0) {
@@ -886,6 +906,7 @@ int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *se
         const char *wz = getenv("SSS_HIP_MERGE_W");
         d.mg_W = (wz && *wz) ? atoi(wz) : 4;
         d.mg_W = d.mg_W >= 4 ? 4 : d.mg_W >= 2 ? 2 : 1;
+        d.mg_acc = merge_acc(d.mg_G, d.mg_two);
         d.ngrid = (d.mg_ng + 4 / d.mg_W - 1) / (4 / d.mg_W);
         d.mg_gp = dev_alloc<int>(gp.size());
         d.mg_k = dev_alloc<unsigned>(mk.size());
@@ -1261,7 +1282,8 @@ __global__ __launch_bounds__(kBlock) void spmv_wave(int n, const int *__restrict
 }
 
 // Free order, merged row groups (DevCSR::mg_*): W waves per group of G rows (merged_block).
-template <int OP, bool NORM, int G>
+// (LDSACC: the lanes' accumulators in LDS, DevCSR::mg_acc)
+template <int OP, bool NORM, int G, bool LDSACC = false>
 __global__ __launch_bounds__(kBlock) void spmv_merged(int n, int ng, int W, const int *__restrict__ gp,
                                                       const unsigned *__restrict__ mk, const double *__restrict__ mv,
                                                       const double *__restrict__ x, const double *__restrict__ b,
@@ -1270,9 +1292,11 @@ __global__ __launch_bounds__(kBlock) void spmv_merged(int n, int ng, int W, cons
 {
     __shared__ double red[8 * G];
     __shared__ double nred[kBlock / 64];
+    __shared__ double acc[LDSACC ? 4 * G * kMergeAccDoubles : 1];
     int g = 0, u = 0;
     double sr = 0.0, unused = 0.0, sq = 0.0;
-    if (merged_block<G, 1>(gp, ng, W, mk, mv, [&](int c) -> double { return x[c]; }, red, g, u, sr, unused)) {
+    if (merged_block<G, 1, LDSACC>(gp, ng, W, mk, mv, [&](int c) -> double { return x[c]; }, red, acc, g, u, sr,
+                                   unused)) {
         const int r = g * G + u;
         if (r < n) {
             bool write = true;
@@ -1298,8 +1322,14 @@ template <int OP, bool NORM>
 static void launch_op(const DevCSR &A, double alpha, const double *x, const double *b, double *y, int cap,
                       double *partial, hipStream_t s)
 {
-    if (A.mg_G == 8)
+    if (A.mg_G == 8 && A.mg_acc)
+        hipLaunchKernelGGL((spmv_merged<OP, NORM, 8, true>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
+                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
+    else if (A.mg_G == 8)
         hipLaunchKernelGGL((spmv_merged<OP, NORM, 8>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
+                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
+    else if (A.mg_G == 4 && A.mg_acc)
+        hipLaunchKernelGGL((spmv_merged<OP, NORM, 4, true>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
                            A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
     else if (A.mg_G == 4)
         hipLaunchKernelGGL((spmv_merged<OP, NORM, 4>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,

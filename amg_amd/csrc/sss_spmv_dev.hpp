@@ -1034,22 +1034,120 @@ __device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__re
         }
 }
 
+// The same sums with the lane's accumulators in LDS (DevCSR::mg_acc): acc is this wave's
+// [S * G][64] doubles, accumulator a = segment * G + row, lane l owning column l of each.  Every
+// product is added to its own accumulator only (one LDS fp64 add per entry) instead of being
+// offered to all S * G register accumulators (a compare, two selects and an add each).
+// The sums keep their bits: in the register form an accumulator receives its own products in
+// increasing position and +0.0 for every foreign entry; s + 0.0 == s for every s but -0.0, and an
+// accumulator is never -0.0 (it starts at +0.0, and (+0.0) + (-0.0) = +0.0), so dropping the
+// foreign adds changes nothing.  A lane's LDS operations complete in issue order and no lane
+// touches another's column, so the order of a lane's own adds is the register form's; the
+// butterfly and the W-combine are unchanged.  The stride between accumulators is 512 B: the bank
+// depends on the lane only, 16 consecutive lanes cover the 32 banks once (no conflicts).
+// A wave takes its entries in batches of up to U chunks of 64; the bounds are the same in every
+// lane, so the batch's chunk count C is a scalar and each count has its own straight-line code
+// (merged_batch_lds<C>): one base pointer plus constant offsets, every key and value load, then
+// every gather, issued before any product.  Only the batch's last chunk can be partial: its lanes
+// past the group read the group's last entry and add +0.0 to that entry's accumulator (an
+// identity, as above).
+constexpr int kMergeAccDoubles = 64;   // per accumulator and wave
+template <int S>
+constexpr int kMergeLdsChunks = S == 2 ? 6 : 8;   // chunks per batch (U changes no sum)
+template <int G, int S, int C, class Fetch>
+__device__ __forceinline__ void merged_batch_lds(const unsigned *__restrict__ pk, const double *__restrict__ pv,
+                                                 int last_n, Fetch fetch, double *mine)
+{
+    const int lane = threadIdx.x & 63;
+    const int ll = min(lane, last_n - 1);   // the last chunk holds last_n (1 ... 64) entries
+    unsigned q[C];
+    double a[C], xv[C];
+#pragma unroll
+    for (int t = 0; t < C; ++t) {
+        const int o = 64 * t + (t == C - 1 ? ll : lane);
+        q[t] = pk[o];
+        a[t] = pv[o];
+    }
+#pragma unroll
+    for (int t = 0; t < C; ++t) xv[t] = fetch((int)(q[t] >> kMergeShift));
+#pragma unroll
+    for (int t = 0; t < C; ++t) {
+        // key = segment << 3 | row with row < G by construction (build_merged); the masks keep any
+        // key inside the wave's S * G accumulators
+        const unsigned key = q[t] & ((1u << kMergeShift) - 1);
+        const unsigned slot = S == 2 ? (key >> 3) * G + (key & (G - 1)) : key & (G - 1);
+        double p = a[t] * xv[t];
+        if (t == C - 1) p = lane < last_n ? p : 0.0;
+        atomicAdd(&mine[slot * kMergeAccDoubles], p);   // ds_add_f64, no return value
+    }
+}
+// (nch is the same in every lane: a chain of scalar branches)
+template <int G, int S, int C, class Fetch>
+__device__ __forceinline__ void merged_batch_dispatch(int nch, const unsigned *__restrict__ pk,
+                                                      const double *__restrict__ pv, int last_n, Fetch fetch,
+                                                      double *mine)
+{
+    if constexpr (C == 1) {
+        merged_batch_lds<G, S, 1>(pk, pv, last_n, fetch, mine);
+    } else {
+        if (nch == C) merged_batch_lds<G, S, C>(pk, pv, last_n, fetch, mine);
+        else merged_batch_dispatch<G, S, C - 1>(nch, pk, pv, last_n, fetch, mine);
+    }
+}
+template <int G, int S, class Fetch>
+__device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *__restrict__ mk,
+                                                const double *__restrict__ mv, Fetch fetch, double *acc,
+                                                double (&s0)[G], double (&s1)[G])
+{
+    constexpr int U = kMergeLdsChunks<S>;
+    const int lane = threadIdx.x & 63;
+    double *mine = acc + lane;
+#pragma unroll
+    for (int a = 0; a < S * G; ++a) mine[a * kMergeAccDoubles] = 0.0;
+    // (wave-uniform: scalar loop control and base pointers)
+    k1 = __builtin_amdgcn_readfirstlane(k1);
+    for (int kb = __builtin_amdgcn_readfirstlane(k0); kb < k1; kb += 64 * U) {
+        const int rem = min(k1 - kb, 64 * U), nch = (rem + 63) >> 6, last_n = rem - 64 * (nch - 1);
+        const unsigned *pk = mk + kb;
+        const double *pv = mv + kb;
+        merged_batch_dispatch<G, S, U>(nch, pk, pv, last_n, fetch, mine);
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+        s0[u] = mine[u * kMergeAccDoubles];
+        s1[u] = S == 2 ? mine[(G + u) * kMergeAccDoubles] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            s0[u] += __shfl_xor(s0[u], off, 64);
+            if (S == 2) s1[u] += __shfl_xor(s1[u], off, 64);
+        }
+}
+
 // Merged groups per 256-thread workgroup: W waves per group (W = 1, 2 or 4, DevCSR::mg_W), so
 // 4 / W groups per workgroup; the waves of a group take consecutive 1/W shares of its entries
 // (merged_sums each), then thread t < (4/W) G reports (group t / G, row t % G): the W partials
 // added in wave order (fixed: deterministic).  Returns false for threads without a row.
 // red: 8G doubles of LDS.  Must be reached by every thread of the block.
-template <int G, int S, class Fetch>
+// LDSACC: the lanes' accumulators in acc, 4 * S * G * kMergeAccDoubles doubles of LDS
+// (merged_sums_lds; acc unused otherwise).
+template <int G, int S, bool LDSACC, class Fetch>
 __device__ __forceinline__ bool merged_block(const int *__restrict__ gp, int ng, int W, const unsigned *__restrict__ mk,
-                                             const double *__restrict__ mv, Fetch fetch, double *red, int &g_out,
-                                             int &u_out, double &t0, double &t1)
+                                             const double *__restrict__ mv, Fetch fetch, double *red, double *acc,
+                                             int &g_out, int &u_out, double &t0, double &t1)
 {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, gpb = 4 / W;
     const int g = xcd_bid() * gpb + w / W, part = w % W;
     double s0[G], s1[G];
     if (g < ng) {
         const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + W - 1) / W;
-        merged_sums<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch, s0, s1);
+        if constexpr (LDSACC)
+            merged_sums_lds<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch,
+                                  acc + w * (S * G * kMergeAccDoubles), s0, s1);
+        else
+            merged_sums<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch, s0, s1);
     } else {
 #pragma unroll
         for (int u = 0; u < G; ++u) s0[u] = 0.0, s1[u] = 0.0;

@@ -36,7 +36,7 @@ def main():
     lvl = 0
     for name, s, e in rows:
         dur = (e - s) / 1e3   # us
-        m = re.search(r"(spmv_\w+)<(\d), (true|false)(?:, \w+)?>", name)
+        m = re.search(r"(spmv_\w+)<(\d), (true|false)(?:, \w+)*>", name)
         # the outer residual norm ends a cycle: the fused-norm SpMV, or relax_range<3> (its F half
         # fused with the next cycle's first F pass, SmootherPlan::pend_ok)
         if (m and m.group(2) == "2" and m.group(3) == "true") or "relax_range<3" in name:
