@@ -336,6 +336,18 @@ inline void with_tile_kind(const DevCSR &A, F f)
         f(std::integral_constant<int, 0>{});
     }
 }
+// f(std::integral_constant<int, G>, std::bool_constant<LDSACC>) with the group size (4 or 8) and the
+// accumulator placement (DevCSR::mg_acc) of A's merged row groups; false, f not called, if A has none
+template <class F>
+inline bool with_merged_kind(const DevCSR &A, F f)
+{
+    if (A.mg_G == 8 && A.mg_acc) f(std::integral_constant<int, 8>{}, std::true_type{});
+    else if (A.mg_G == 8) f(std::integral_constant<int, 8>{}, std::false_type{});
+    else if (A.mg_G == 4 && A.mg_acc) f(std::integral_constant<int, 4>{}, std::true_type{});
+    else if (A.mg_G == 4) f(std::integral_constant<int, 4>{}, std::false_type{});
+    else return false;
+    return true;
+}
 
 // ---- stored-format byte ledger (bench.py `vcycle_stored`, tools/level_breakdown.py) -------------
 // While a ledger is installed on the calling thread (sss_hip_cycle_bytes: one eager walk of the

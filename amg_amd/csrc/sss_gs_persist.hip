@@ -321,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void gs_flow_group(int nchunks, const int *
         if (active && gl == 0) {
             const double d = dr;
             // natural order (Solve/SSS_smooth.c:112): x_i = t * d, d the carried reciprocal
-            const double xn = NAT ? acc * d : fabs(d) > SMALLFLOAT ? acc / d : x_own(x, i);
+            const double xn = NAT ? acc * d : div_ok(d) ? acc / d : x_own(x, i);
             // the granules first: this pass's readers of x_i wait on them, x itself is read later
             granule_put(gran + 2 * (size_t)(i - lo), epoch, xn);
             if (trace) {
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(kBlock) void gs_fused_group(int nchunks, const int 
         if (active && gl == 0) {
             unsigned long long *own = gran + 2 * (size_t)i;
             double xn;
-            if (fabs(dr) > SMALLFLOAT) xn = acc / dr;
+            if (div_ok(dr)) xn = acc / dr;
             else xn = s == 0 ? x_own(x, i) : granule_wait(own, tag(s), err, spin);   // unchanged
             // a row without neighbours is ordered after its previous update only here
             if (s > 0 && !linked) (void)granule_wait(own, tag(s), err, spin);
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(64 * kCuWaves) void gs_cu(int nrows, int ndepth, co
         }
         if (lane == 0) {
             const double dd = deff[i];
-            if (fabs(dd) > SMALLFLOAT) x[i] = acc / dd;
+            if (div_ok(dd)) x[i] = acc / dd;
             // release: the x store above is visible to every wave of the workgroup that acquires
             // this counter
             __hip_atomic_fetch_add(&done[d], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);

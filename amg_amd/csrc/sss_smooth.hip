@@ -417,7 +417,7 @@ __global__ __launch_bounds__(kBlock) void gs_depth_thread(const int *__restrict_
     }
     const double d = deff[i];
     if (NAT) x[i] = acc * d;
-    else if (fabs(d) > SMALLFLOAT) x[i] = acc / d;
+    else if (div_ok(d)) x[i] = acc / d;
 }
 
 // exact GS on long rows: four rows of the current depth per workgroup, one per wave; lanes
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kBlock) void gs_depth_wave(const int *__restrict__ 
     if ((threadIdx.x & 63) == 0) {
         const double d = deff[i];
         if (NAT) x[i] = acc * d;
-        else if (fabs(d) > SMALLFLOAT) x[i] = acc / d;
+        else if (div_ok(d)) x[i] = acc / d;
     }
 }
 
@@ -455,9 +455,9 @@ __global__ __launch_bounds__(kBlock) void relax_compact(const int *__restrict__ 
     csr_block_relax(blk, rp, ci, v, map, b, x, sm, [&](int r, int i, double acc) {
         const double d = deff[i];
         if (INPLACE) {
-            if (fabs(d) > SMALLFLOAT) x[i] = acc / d;
+            if (div_ok(d)) x[i] = acc / d;
         } else {
-            y[r] = fabs(d) > SMALLFLOAT ? acc / d : x[i];
+            y[r] = div_ok(d) ? acc / d : x[i];
         }
     });
 }
@@ -479,9 +479,9 @@ __global__ __launch_bounds__(kBlock) void relax_wave(int m, const int *__restric
     if ((threadIdx.x & 63) == 0) {
         const double d = deff[i];
         if (INPLACE) {
-            if (fabs(d) > SMALLFLOAT) x[i] = acc / d;
+            if (div_ok(d)) x[i] = acc / d;
         } else {
-            y[r] = fabs(d) > SMALLFLOAT ? acc / d : x[i];
+            y[r] = div_ok(d) ? acc / d : x[i];
         }
     }
 }
@@ -499,6 +499,64 @@ __global__ __launch_bounds__(kBlock) void relax_wave(int m, const int *__restric
 // |d| <= 1e-20 keep their value.
 // Dictionary ELL rows (DICT == 2): the same per-row arithmetic, the row's products in registers in
 // stored (slot) order instead of staged in LDS.
+// The row formula of all four modes over a row's products in stored order, whatever holds them:
+// pr.sub(s, a, e) / pr.add(s, a, e) = s -/+ the products of slots [a, e) (EllProds: registers;
+// XellProds: column-ELL codes and LDS values; TileProds: the LDS tile).  The row's slots are [a, e),
+// its diagonal at slot ds when diag; br = b_r, div() the divisor (asked for after the chain: the tile
+// path reads it only then), keep() the value a row with a failing divisor keeps (read only then).  xn: the relaxed value; res: the row's residual (MODE 2: with the
+// new x_r in the diagonal product, MODE 3: with x unchanged); upd: the divisor passed div_ok.
+struct RelaxRow {
+    double xn, res;
+    bool upd;
+};
+// br - the row's off-diagonal products in stored order (Solve/SSS_smooth.c:21-26)
+template <class Prods>
+__device__ __forceinline__ double relax_acc(const Prods &pr, int a, bool diag, int ds, int e, double br)
+{
+    if (!diag) return pr.sub(br, a, e);
+    return pr.sub(pr.sub(br, a, ds), ds + 1, e);
+}
+template <int MODE, class Prods, class Div, class Keep>
+__device__ __forceinline__ RelaxRow relax_row(const Prods &pr, int a, bool diag, int ds, int e, double br, Div div,
+                                              Keep keep)
+{
+    const double acc = relax_acc(pr, a, diag, ds, e, br);
+    const double d = div();
+    RelaxRow o;
+    o.upd = div_ok(d);
+    o.xn = o.upd ? acc / d : keep();
+    o.res = 0.0;
+    if constexpr (MODE == 2) {   // plans guarantee one diagonal per row here
+        double t = pr.add(0.0, a, ds);
+        t += d * o.xn;
+        t = pr.add(t, ds + 1, e);
+        o.res = br + t * -1.0;
+    } else if constexpr (MODE == 3) {
+        o.res = br + pr.add(0.0, a, e) * -1.0;
+    }
+    return o;
+}
+template <int W>
+struct EllProds {
+    const double (&p)[W];
+    __device__ __forceinline__ double sub(double s, int a, int e) const { return ell_sub(s, p, a, e); }
+    __device__ __forceinline__ double add(double s, int a, int e) const { return ell_add(s, p, a, e); }
+};
+template <int W>
+struct XellProds {
+    const unsigned (&w)[W];
+    const double (&xv)[W];
+    const XellSmem &es;
+    int shift;
+    __device__ __forceinline__ double sub(double s, int a, int e) const { return xell_sum_g<true>(s, w, xv, es, shift, a, e); }
+    __device__ __forceinline__ double add(double s, int a, int e) const { return xell_sum_g<false>(s, w, xv, es, shift, a, e); }
+};
+struct TileProds {
+    const double *v;
+    __device__ __forceinline__ double sub(double s, int a, int e) const { return chain_sub(s, v, a, e); }
+    __device__ __forceinline__ double add(double s, int a, int e) const { return chain_add(s, v, a, e); }
+};
+
 template <int MODE, int W>
 __device__ __forceinline__ void relax_range_ell(int blo, const int2 *__restrict__ blk, int lo,
                                                 const double *__restrict__ b, double *x, double *__restrict__ y,
@@ -508,66 +566,42 @@ __device__ __forceinline__ void relax_range_ell(int blo, const int2 *__restrict_
     constexpr int RPT = kEllRpt;
     __shared__ EllSmem es[RPT];
     const int g = (int)blockIdx.x;
-    unsigned w[RPT][W / 4];
+    EllRow<W> row[RPT];
     double br[RPT], dr[RPT];
-    int r[RPT];
-    bool live[RPT], valid[RPT];
 #pragma unroll
     for (int j = 0; j < RPT; ++j) {   // every row's codes, b and divisor in flight across the barrier
-        const int bid = blo + g * RPT + j;
-        valid[j] = bid < dt.bend;
-        live[j] = false;
         br[j] = dr[j] = 0.0;
-        r[j] = 0;
-#pragma unroll
-        for (int t = 0; t < W / 4; ++t) w[j][t] = 0u;
-        if (valid[j]) {
-            const int2 ba = blk[bid], be = blk[bid + 1];
-            r[j] = ba.x + (int)threadIdx.x;
-            live[j] = r[j] < be.x;
-            if (live[j]) {
-                ell_codes<W>(dt.ell, r[j], w[j]);
-                br[j] = b[r[j]];
-                if (deff) dr[j] = deff[r[j]];
-            }
-            ell_load_dicts_nosync(dt, bid, es[j]);
-        }
+        row[j] = ell_row_begin<W>(blk, blo + g * RPT + j, dt, es[j], [&](int r) {
+            br[j] = b[r];
+            if (deff) dr[j] = deff[r];
+        });
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < RPT; ++j) {
         double sq = 0.0;
-        if (live[j]) {
-            const int rj = r[j];
+        if (row[j].live) {
+            const int rj = row[j].r;
             double p[W];
             int dsl;
             double dv;
             // the pass's own x_r only in MODE 3 (the residual of the row with x unchanged)
-            const int len = ell_decode<W, MODE == 3>(w[j], rj, es[j], [&](int c) -> double { return xs(c); }, p, dsl, dv);
-            const double acc = dsl < 0 ? ell_sub(br[j], p, 0, len) : ell_sub(ell_sub(br[j], p, 0, dsl), p, dsl + 1, len);
-            const double d = deff ? dr[j] : dv;
-            if constexpr (MODE == 2) {
-                const double xn = fabs(d) > SMALLFLOAT ? acc / d : x[rj];
-                if (fabs(d) > SMALLFLOAT) x[rj] = xn;
-                double t = ell_add(0.0, p, 0, dsl);
-                t += d * xn;
-                t = ell_add(t, p, dsl + 1, len);
-                const double out = br[j] + t * -1.0;
-                rr[rj] = out;
-                sq = out * out;
-            } else if constexpr (MODE == 3) {
-                const double out = br[j] + ell_add(0.0, p, 0, len) * -1.0;
-                rr[rj] = out;
-                sq = out * out;
-                y[rj - lo] = fabs(d) > SMALLFLOAT ? acc / d : x[rj];
-            } else if constexpr (MODE == 1) {
-                y[rj - lo] = fabs(d) > SMALLFLOAT ? acc / d : xs(rj);
+            const int len = ell_decode<W, MODE == 3>(row[j].w, rj, es[j], [&](int c) -> double { return xs(c); }, p, dsl, dv);
+            const RelaxRow o = relax_row<MODE>(EllProds<W>{p}, 0, dsl >= 0, dsl, len, br[j], [&] { return deff ? dr[j] : dv; }, [&]() -> double {
+                return MODE == 0 ? 0.0 : MODE == 1 ? xs(rj) : x[rj];   // (MODE 0 stores only an updated row)
+            });
+            if constexpr (MODE == 0 || MODE == 2) {
+                if (o.upd) x[rj] = o.xn;
             } else {
-                if (fabs(d) > SMALLFLOAT) x[rj] = acc / d;
+                y[rj - lo] = o.xn;
+            }
+            if constexpr (MODE >= 2) {
+                rr[rj] = o.res;
+                sq = o.res * o.res;
             }
         }
         if constexpr (MODE >= 2) {
-            if (partial && valid[j]) {   // (valid is uniform over the workgroup)
+            if (partial && row[j].valid) {   // (valid is uniform over the workgroup)
                 const double t = block_sum(sq, es[j].red);
                 if (threadIdx.x == 0) partial[blo + g * RPT + j] = t;
             }
@@ -604,24 +638,13 @@ __device__ __forceinline__ void relax_range_ell2(int blo, const int2 *__restrict
         int dsl;
         double dv;
         const int len = ell_decode<8, MODE == 3>(w[i], rj, es[j], [&](int c) -> double { return xs(c); }, p, dsl, dv);
-        const double acc = dsl < 0 ? ell_sub(br[i], p, 0, len) : ell_sub(ell_sub(br[i], p, 0, dsl), p, dsl + 1, len);
-        const double d = deff ? dr[i] : dv;
-        if constexpr (MODE == 2) {
-            const double xn = fabs(d) > SMALLFLOAT ? acc / d : x[rj];
-            xo[i] = xn;
-            double t = ell_add(0.0, p, 0, dsl);
-            t += d * xn;
-            t = ell_add(t, p, dsl + 1, len);
-            ro[i] = br[i] + t * -1.0;
+        // (the pair is stored whole: a row with a failing divisor stores the value it keeps)
+        const RelaxRow o = relax_row<MODE>(EllProds<8>{p}, 0, dsl >= 0, dsl, len, br[i], [&] { return deff ? dr[i] : dv; },
+                                           [&]() -> double { return MODE == 1 ? xs(rj) : x[rj]; });
+        xo[i] = o.xn;
+        if constexpr (MODE >= 2) {
+            ro[i] = o.res;
             sq[j] += ro[i] * ro[i];
-        } else if constexpr (MODE == 3) {
-            ro[i] = br[i] + ell_add(0.0, p, 0, len) * -1.0;
-            sq[j] += ro[i] * ro[i];
-            xo[i] = fabs(d) > SMALLFLOAT ? acc / d : x[rj];
-        } else if constexpr (MODE == 1) {
-            xo[i] = fabs(d) > SMALLFLOAT ? acc / d : xs(rj);
-        } else {
-            xo[i] = fabs(d) > SMALLFLOAT ? acc / d : x[rj];   // (a row with |d| <= 1e-20 keeps its value)
         }
     }
     if constexpr (MODE == 0 || MODE == 2) pair_store(x, pr.r, pr.l0, pr.l1, xo);
@@ -660,52 +683,31 @@ __device__ __forceinline__ void relax_range_xell(int blo, const int2 *__restrict
     __shared__ XellSmem es;
     const int bid = blo + (int)blockIdx.x;
     const bool valid = bid < dt.bend;
-    unsigned w[W];
     double br = 0.0, dr = 0.0;
-    int r = 0;
-    bool live = false;
-#pragma unroll
-    for (int t = 0; t < W; ++t) w[t] = 0xffffffffu;
-    if (valid) {   // the row's codes, b and divisor in flight across the barrier
-        const int2 ba = blk[bid], be = blk[bid + 1];
-        r = ba.x + (int)threadIdx.x;
-        live = r < be.x;
-        if (live) {
-            xell_codes<W>(dt.xell, r, w);
-            br = b[r];
-            if (deff) dr = deff[r];
-        }
-        xell_load_dict_nosync(dt, bid, es);
-    }
+    const XellRow<W> row = xell_row_begin<W>(valid, blk, bid, dt.xell, dt.pd, dt.vd, es, [&](int r) {
+        br = b[r];
+        if (deff) dr = deff[r];
+    });
+    const unsigned(&w)[W] = row.w;
+    const int r = row.r;
     __syncthreads();
     double sq = 0.0;
-    if (live) {
+    if (row.live) {
         double xv[W];
         int dsl;
         unsigned dcode;
         const int len = xell_gather<W, MODE == 3>(w, r, dt.xshift, [&](int c) -> double { return xs(c); }, xv, dsl, dcode);
-        const double acc = dsl < 0 ? xell_sub(br, w, xv, es, dt.xshift, 0, len)
-                                   : xell_sub(xell_sub(br, w, xv, es, dt.xshift, 0, dsl), w, xv, es, dt.xshift, dsl + 1, len);
         const double dv = dsl < 0 ? 0.0 : es.vd[dcode >> dt.xshift];
-        const double d = deff ? dr : dv;
-        if constexpr (MODE == 2) {
-            const double xn = fabs(d) > SMALLFLOAT ? acc / d : x[r];
-            if (fabs(d) > SMALLFLOAT) x[r] = xn;
-            double t = xell_add(0.0, w, xv, es, dt.xshift, 0, dsl);
-            t += d * xn;
-            t = xell_add(t, w, xv, es, dt.xshift, dsl + 1, len);
-            const double out = br + t * -1.0;
-            rr[r] = out;
-            sq = out * out;
-        } else if constexpr (MODE == 3) {
-            const double out = br + xell_add(0.0, w, xv, es, dt.xshift, 0, len) * -1.0;
-            rr[r] = out;
-            sq = out * out;
-            y[r - lo] = fabs(d) > SMALLFLOAT ? acc / d : x[r];
-        } else if constexpr (MODE == 1) {
-            y[r - lo] = fabs(d) > SMALLFLOAT ? acc / d : xs(r);
+        const RelaxRow o = relax_row<MODE>(XellProds<W>{w, xv, es, dt.xshift}, 0, dsl >= 0, dsl, len, br, [&] { return deff ? dr : dv; },
+                                           [&]() -> double { return MODE == 0 ? 0.0 : MODE == 1 ? xs(r) : x[r]; });
+        if constexpr (MODE == 0 || MODE == 2) {
+            if (o.upd) x[r] = o.xn;
         } else {
-            if (fabs(d) > SMALLFLOAT) x[r] = acc / d;
+            y[r - lo] = o.xn;
+        }
+        if constexpr (MODE >= 2) {
+            rr[r] = o.res;
+            sq = o.res * o.res;
         }
     }
     if constexpr (MODE >= 2) {
@@ -747,44 +749,34 @@ __device__ __forceinline__ void relax_range_body(int blo, const int2 *__restrict
     auto finish = [&](int r, double acc) {
         const double d = dval(r);
         if (MODE != 1) {
-            if (fabs(d) > SMALLFLOAT) x[r] = acc / d;
+            if (div_ok(d)) x[r] = acc / d;
         } else {
-            y[r - lo] = fabs(d) > SMALLFLOAT ? acc / d : xs(r);
+            y[r - lo] = div_ok(d) ? acc / d : xs(r);
         }
     };
     if (k1 - k0 <= kTileEntries) {
         const int r = r0 + (int)threadIdx.x;
         int a = 0, e = 0, dp = -1;
-        double acc = 0.0, br = 0.0;
+        double br = 0.0;
         if (r < r1) a = rp[r] - k0, e = rp[r + 1] - k0, dp = diag_pos[r], br = b[r];   // ahead of the tile
         stage_any(sm.v, k0, k1, ci, v, pk, pv, pb, bid, r0, deff ? (double *)nullptr : sm.d, fetch, dt, ds, r1, rp);
         __syncthreads();
         double sq = 0.0;
         if (r < r1) {
-            acc = br;
-            if (dp < 0) acc = chain_sub(acc, sm.v, a, e);
-            else {
-                acc = chain_sub(acc, sm.v, a, dp - k0);
-                acc = chain_sub(acc, sm.v, dp - k0 + 1, e);
-            }
-            if constexpr (MODE == 2) {   // plan guarantees one diagonal per row, deff = a_rr
-                const double d = dval(r);
-                const double xn = fabs(d) > SMALLFLOAT ? acc / d : x[r];
-                if (fabs(d) > SMALLFLOAT) x[r] = xn;
-                double s = chain_add(0.0, sm.v, a, dp - k0);
-                s += d * xn;
-                s = chain_add(s, sm.v, dp - k0 + 1, e);
-                const double out = br + s * -1.0;
-                rr[r] = out;
-                sq = out * out;
-            } else if constexpr (MODE == 3) {   // residual of the row (x unchanged) + its GS value
-                const double out = br + chain_add(0.0, sm.v, a, e) * -1.0;
-                rr[r] = out;
-                sq = out * out;
-                const double d = dval(r);
-                y[r - lo] = fabs(d) > SMALLFLOAT ? acc / d : x[r];
+            if constexpr (MODE >= 2) {
+                const RelaxRow o = relax_row<MODE>(TileProds{sm.v}, a, dp >= 0, dp - k0, e, br, [&] { return dval(r); },
+                                                   [&]() -> double { return x[r]; });
+                if constexpr (MODE == 2) {
+                    if (o.upd) x[r] = o.xn;
+                } else {
+                    y[r - lo] = o.xn;
+                }
+                rr[r] = o.res;
+                sq = o.res * o.res;
             } else {
-                finish(r, acc);
+                // (not relax_row: with it the dictionary-tile relax_range_occ<0, 1> compiled to 34
+                // scalar-register spills instead of 22)
+                finish(r, relax_acc(TileProds{sm.v}, a, dp >= 0, dp - k0, e, br));
             }
         }
         if constexpr (MODE >= 2) {
@@ -795,27 +787,28 @@ __device__ __forceinline__ void relax_range_body(int blo, const int2 *__restrict
         }
     } else if constexpr (MODE < 2) {   // MODE 2 / 3 plans have no long-row block
         const int r = r0, dp = diag_pos[r];
-        double acc = b[r];
-        for (int base = k0; base < k1; base += kTileEntries) {
-            const int m = min(kTileEntries, k1 - base);
-            stage_any(sm.v, base, base + m, ci, v, pk, pv, pb, bid, r0, deff ? (double *)nullptr : sm.d, fetch, dt, ds,
-                      r1, rp);
-            __syncthreads();
-            if (dt.tree_long) {   // free order: acc -= tree sum of the chunk's off-diagonal products
-                if (threadIdx.x == 0 && dp >= base && dp < base + m) sm.v[dp - base] = 0.0;
-                __syncthreads();
-                const double c = block_tree_sum(sm.v, 0, m, sm.red);
-                if (threadIdx.x == 0) acc -= c;
-            } else if (threadIdx.x == 0) {
-                if (dp >= base && dp < base + m) {
-                    acc = chain_sub(acc, sm.v, 0, dp - base);
-                    acc = chain_sub(acc, sm.v, dp - base + 1, m);
-                } else {
-                    acc = chain_sub(acc, sm.v, 0, m);
+        const double acc = long_row_chunks(
+            k0, k1, b[r],
+            [&](int base, int m) {
+                stage_any(sm.v, base, base + m, ci, v, pk, pv, pb, bid, r0, deff ? (double *)nullptr : sm.d, fetch, dt,
+                          ds, r1, rp);
+            },
+            [&](int base, int m, double acc) {
+                if (dt.tree_long) {   // free order: acc -= tree sum of the chunk's off-diagonal products
+                    if (threadIdx.x == 0 && dp >= base && dp < base + m) sm.v[dp - base] = 0.0;
+                    __syncthreads();
+                    const double c = block_tree_sum(sm.v, 0, m, sm.red);
+                    if (threadIdx.x == 0) acc -= c;
+                } else if (threadIdx.x == 0) {
+                    if (dp >= base && dp < base + m) {
+                        acc = chain_sub(acc, sm.v, 0, dp - base);
+                        acc = chain_sub(acc, sm.v, dp - base + 1, m);
+                    } else {
+                        acc = chain_sub(acc, sm.v, 0, m);
+                    }
                 }
-            }
-            __syncthreads();
-        }
+                return acc;
+            });
         if (threadIdx.x == 0) finish(r, acc);
     }
     }
@@ -877,9 +870,9 @@ __global__ __launch_bounds__(kBlock) void relax_range_wave(int lo, int hi, const
     if ((threadIdx.x & 63) == 0) {
         const double d = deff[r];
         if (MODE == 0) {
-            if (fabs(d) > SMALLFLOAT) x[r] = acc / d;
+            if (div_ok(d)) x[r] = acc / d;
         } else {
-            y[r - lo] = fabs(d) > SMALLFLOAT ? acc / d : xs(r);
+            y[r - lo] = div_ok(d) ? acc / d : xs(r);
         }
     }
 }
@@ -897,39 +890,33 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
     auto finish = [&](int q, double acc) {
         const int r = lo + q;
         const double d = deff[r];
-        y[q] = fabs(d) > SMALLFLOAT ? acc / d : x(r);
+        y[q] = div_ok(d) ? acc / d : x(r);
     };
     if constexpr (PATH >= kXell) {   // column ELL rows of width PATH - kXell: one thread per row
         constexpr int W = PATH - kXell;
         __shared__ XellSmem es;
         const int bq = blockIdx.x;
-        const int2 ba = M.bk[bq], be = M.bk[bq + 1];
-        const int q = ba.x + (int)threadIdx.x;
-        const bool live = q < be.x;
-        unsigned w[W];
         double bq_v = 0.0, dq = 0.0;
         int sp = 0;
-#pragma unroll
-        for (int t = 0; t < W; ++t) w[t] = 0xffffffffu;
-        if (live) {   // the row's codes, b, divisor and its [N | L] cut in flight across the barrier
-            xell_codes<W>(M.dv_xell, q, w);
+        // (the row's b, divisor and its [N | L] cut with the codes)
+        const XellRow<W> row = xell_row_begin<W>(true, M.bk, bq, M.dv_xell, M.dv_pd, M.dv_vd, es, [&](int q) {
             bq_v = b[lo + q];
             dq = deff[lo + q];
             sp = split[q] - M.rp[q];
-        }
-        {
-            const int4 pq4 = M.dv_pd[bq];
-            for (int t = threadIdx.x; t < pq4.w; t += kBlock) es.vd[t] = M.dv_vd[pq4.z + t];
-        }
+        });
+        const unsigned(&w)[W] = row.w;
+        const int q = row.r;
+        const bool live = row.live;
         __syncthreads();
         if (live) {
             double xv[W];
             int ds;
-            const int len = xell_gather<W>(w, -1, M.xell_shift, [&](int c) -> double { return x(c); }, xv, ds);
+            unsigned dcode;
+            const int len = xell_gather<W>(w, -1, M.xell_shift, [&](int c) -> double { return x(c); }, xv, ds, dcode);
             const double Pq = xell_sum_bf<true>(bq_v, w, xv, es, M.xell_shift, 0, sp);
             P[q] = Pq;
             const double acc = xell_sum_bf<true>(Pq, w, xv, es, M.xell_shift, sp, len);
-            y[q] = fabs(dq) > SMALLFLOAT ? acc / dq : x(lo + q);   // finish() with the divisor loaded early
+            y[q] = div_ok(dq) ? acc / dq : x(lo + q);   // finish() with the divisor loaded early
         }
         return;
     } else if constexpr (PATH >= 3) {   // merged row groups, G = PATH, M.mg_W waves per group
@@ -992,31 +979,32 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
             }
         } else {   // one long row, chunk by chunk, thread 0 carries the chain
             const int q = q0, sp = split[q];
-            double acc = b[lo + q];
-            for (int base = k0; base < k1; base += kTileEntries) {
-                const int m = min(kTileEntries, k1 - base);
-                stage_any(sm.v, base, base + m, M.ci, M.v, M.pk, M.pv, M.pb, bq, q0, (double *)nullptr, [&](int c) -> double { return x(c); });
-                __syncthreads();
-                if (M.tree_long) {   // free order: the N part and the L part of the chunk tree-summed
-                    const int cut = min(max(sp - base, 0), m);
-                    const double c1 = block_tree_sum(sm.v, 0, cut, sm.red);
-                    const double c2 = block_tree_sum(sm.v, cut, m, sm.red);
-                    if (threadIdx.x == 0) {
-                        acc -= c1;
-                        if (sp >= base && sp < base + m) P[q] = acc;
-                        acc -= c2;
+            const double acc = long_row_chunks(
+                k0, k1, b[lo + q],
+                [&](int base, int m) {
+                    stage_any(sm.v, base, base + m, M.ci, M.v, M.pk, M.pv, M.pb, bq, q0, (double *)nullptr, [&](int c) -> double { return x(c); });
+                },
+                [&](int base, int m, double acc) {
+                    if (M.tree_long) {   // free order: the N part and the L part of the chunk tree-summed
+                        const int cut = min(max(sp - base, 0), m);
+                        const double c1 = block_tree_sum(sm.v, 0, cut, sm.red);
+                        const double c2 = block_tree_sum(sm.v, cut, m, sm.red);
+                        if (threadIdx.x == 0) {
+                            acc -= c1;
+                            if (sp >= base && sp < base + m) P[q] = acc;
+                            acc -= c2;
+                        }
+                    } else if (threadIdx.x == 0) {
+                        if (sp >= base && sp < base + m) {
+                            acc = chain_sub(acc, sm.v, 0, sp - base);
+                            P[q] = acc;
+                            acc = chain_sub(acc, sm.v, sp - base, m);
+                        } else {
+                            acc = chain_sub(acc, sm.v, 0, m);
+                        }
                     }
-                } else if (threadIdx.x == 0) {
-                    if (sp >= base && sp < base + m) {
-                        acc = chain_sub(acc, sm.v, 0, sp - base);
-                        P[q] = acc;
-                        acc = chain_sub(acc, sm.v, sp - base, m);
-                    } else {
-                        acc = chain_sub(acc, sm.v, 0, m);
-                    }
-                }
-                __syncthreads();
-            }
+                    return acc;
+                });
             if (threadIdx.x == 0) {
                 if (sp == k1) P[q] = acc;   // no L entries
                 finish(q, acc);
@@ -1035,35 +1023,29 @@ __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const doubl
     auto fetch = [&](int c) -> double { return ycols[c - col_off]; };
     auto finish = [&](int q, double acc) {
         const double d = deff[lo + q];
-        y[q] = fabs(d) > SMALLFLOAT ? acc / d : ykeep[q];
+        y[q] = div_ok(d) ? acc / d : ykeep[q];
     };
     if constexpr (PATH >= kXell) {   // column ELL rows of width PATH - kXell: one thread per row
         constexpr int W = PATH - kXell;
         __shared__ XellSmem es;
         const int bq = blockIdx.x;
-        const int2 ba = M.bk[bq], be = M.bk[bq + 1];
-        const int q = ba.x + (int)threadIdx.x;
-        const bool live = q < be.x;
-        unsigned w[W];
         double pq = 0.0, dq = 0.0;
-#pragma unroll
-        for (int t = 0; t < W; ++t) w[t] = 0xffffffffu;
-        if (live) {   // codes, P_q and the divisor in flight across the barrier
-            xell_codes<W>(M.dv_xell, q, w);
+        // (P_q and the divisor with the codes)
+        const XellRow<W> row = xell_row_begin<W>(true, M.bk, bq, M.dv_xell, M.dv_pd, M.dv_vd, es, [&](int q) {
             pq = P[q];
             dq = deff[lo + q];
-        }
-        {
-            const int4 pq4 = M.dv_pd[bq];
-            for (int t = threadIdx.x; t < pq4.w; t += kBlock) es.vd[t] = M.dv_vd[pq4.z + t];
-        }
+        });
+        const unsigned(&w)[W] = row.w;
+        const int q = row.r;
+        const bool live = row.live;
         __syncthreads();
         if (live) {
             double xv[W];
             int ds;
-            const int len = xell_gather<W>(w, -1, M.xell_shift, fetch, xv, ds);
-            const double acc = xell_sub(pq, w, xv, es, M.xell_shift, 0, len);
-            y[q] = fabs(dq) > SMALLFLOAT ? acc / dq : ykeep[q];   // finish() with the divisor loaded early
+            unsigned dcode;
+            const int len = xell_gather<W>(w, -1, M.xell_shift, fetch, xv, ds, dcode);
+            const double acc = xell_sum_g<true>(pq, w, xv, es, M.xell_shift, 0, len);
+            y[q] = div_ok(dq) ? acc / dq : ykeep[q];   // finish() with the divisor loaded early
         }
         return;
     } else if constexpr (PATH >= 3) {   // merged row groups, G = PATH, M.mg_W waves per group
@@ -1108,19 +1090,20 @@ __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const doubl
             if (q < q1) finish(q, chain_sub(acc, sm.v, a, e));
         } else {
             const int q = q0;
-            double acc = P[q];
-            for (int base = k0; base < k1; base += kTileEntries) {
-                const int m = min(kTileEntries, k1 - base);
-                stage_any(sm.v, base, base + m, M.ci, M.v, M.pk, M.pv, M.pb, bq, q0, (double *)nullptr, fetch);
-                __syncthreads();
-                if (M.tree_long) {
-                    const double c = block_tree_sum(sm.v, 0, m, sm.red);
-                    if (threadIdx.x == 0) acc -= c;
-                } else if (threadIdx.x == 0) {
-                    acc = chain_sub(acc, sm.v, 0, m);
-                }
-                __syncthreads();
-            }
+            const double acc = long_row_chunks(
+                k0, k1, P[q],
+                [&](int base, int m) {
+                    stage_any(sm.v, base, base + m, M.ci, M.v, M.pk, M.pv, M.pb, bq, q0, (double *)nullptr, fetch);
+                },
+                [&](int, int m, double acc) {
+                    if (M.tree_long) {
+                        const double c = block_tree_sum(sm.v, 0, m, sm.red);
+                        if (threadIdx.x == 0) acc -= c;
+                    } else if (threadIdx.x == 0) {
+                        acc = chain_sub(acc, sm.v, 0, m);
+                    }
+                    return acc;
+                });
             if (threadIdx.x == 0) finish(q, acc);
         }
     }
@@ -1141,15 +1124,12 @@ void launch_ts_stage0(const DevCSR &M, int lo, const int *split, const double *b
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + x gathers, b, deff, P and y
-    if (M.mg_G == 8 && M.mg_two && M.mg_acc)
-        hipLaunchKernelGGL((ts_stage0<8, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
-    else if (M.mg_G == 8 && M.mg_two)
-        hipLaunchKernelGGL(ts_stage0<8>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
-    else if (M.mg_G == 4 && M.mg_two && M.mg_acc)
-        hipLaunchKernelGGL((ts_stage0<4, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
-    else if (M.mg_G == 4 && M.mg_two)
-        hipLaunchKernelGGL(ts_stage0<4>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
-    else if (M.vec_rows)
+    if (M.mg_two && with_merged_kind(M, [&](auto G, auto ACC) {
+            hipLaunchKernelGGL((ts_stage0<decltype(G)::value, decltype(ACC)::value>), dim3(M.ngrid), dim3(kBlock), 0, s,
+                               lo, M, split, b, x, deff, P, y);
+        }))
+        return;
+    if (M.vec_rows)
         hipLaunchKernelGGL(ts_stage0<2>, dim3((M.n + 3) / 4), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
     else if (M.wave_rows)
         hipLaunchKernelGGL(ts_stage0<1>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
@@ -1168,17 +1148,12 @@ void launch_ts_inner(const DevCSR &M, int lo, const double *deff, const double *
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + y gathers, deff, P, ykeep and y
-    if (M.mg_G == 8 && M.mg_acc)
-        hipLaunchKernelGGL((ts_inner<8, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off,
-                           ykeep, y);
-    else if (M.mg_G == 8)
-        hipLaunchKernelGGL(ts_inner<8>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
-    else if (M.mg_G == 4 && M.mg_acc)
-        hipLaunchKernelGGL((ts_inner<4, true>), dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off,
-                           ykeep, y);
-    else if (M.mg_G == 4)
-        hipLaunchKernelGGL(ts_inner<4>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
-    else if (M.vec_rows)
+    if (with_merged_kind(M, [&](auto G, auto ACC) {
+            hipLaunchKernelGGL((ts_inner<decltype(G)::value, decltype(ACC)::value>), dim3(M.ngrid), dim3(kBlock), 0, s,
+                               lo, M, deff, P, ycols, col_off, ykeep, y);
+        }))
+        return;
+    if (M.vec_rows)
         hipLaunchKernelGGL(ts_inner<2>, dim3((M.n + 3) / 4), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
     else if (M.wave_rows)
         hipLaunchKernelGGL(ts_inner<1>, dim3(M.ngrid), dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
@@ -1226,7 +1201,7 @@ __global__ __launch_bounds__(kBlock) void zero_first_pass(int lo, int m, const i
         t = zero_x_sum(b[r], ci, v, rp[r], rp[r + 1], r);
     }
     const double d = deff[r];
-    y[q] = fabs(d) > SMALLFLOAT ? t / d : 0.0;   // a row that keeps its value keeps x_r = +0.0
+    y[q] = div_ok(d) ? t / d : 0.0;   // a row that keeps its value keeps x_r = +0.0
 }
 
 int launch_f_residual_pending(const SmootherPlan &sp, const DevCSR &A, const double *b, const double *x, double *r,

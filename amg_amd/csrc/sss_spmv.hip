@@ -1118,6 +1118,32 @@ void devcsr_free(DevCSR &d)
 }
 
 // ---- kernel -------------------------------------------------------------------------------
+// The epilogue of every SpMV kernel: y_r from the row's sum s (br = b_r, read by RESID only); returns
+// the row's contribution to the norm, out^2 (NORM) or 0.
+template <int OP, bool NORM>
+__device__ __forceinline__ double spmv_row_out(int r, double s, double alpha, double br, double *__restrict__ y, int cap)
+{
+    double out;
+    if constexpr (OP == SSS_HIP_SPMV_MXY) out = s;
+    else if constexpr (OP == SSS_HIP_SPMV_AMXPY) out = y[r] + s * alpha;
+    else if constexpr (OP == SSS_HIP_SPMV_RESID) out = br + s * alpha;
+    else {
+        if (cap > 0 && r >= cap) return 0.0;   // as-shipped <<<64,64>>> row cap
+        out = y[r] + s;
+    }
+    y[r] = out;
+    return NORM ? out * out : 0.0;
+}
+// ... with b_r read here (the ELL branches load it ahead of their barrier and pass it in)
+template <int OP, bool NORM>
+__device__ __forceinline__ double spmv_row_out(int r, double s, double alpha, const double *__restrict__ b,
+                                               double *__restrict__ y, int cap)
+{
+    double br = 0.0;
+    if constexpr (OP == SSS_HIP_SPMV_RESID) br = b[r];
+    return spmv_row_out<OP, NORM>(r, s, alpha, br, y, cap);
+}
+
 template <int OP, bool NORM, int DICT = 0>   // DICT: with_tile_kind (8/16/32: dictionary ELL, that width)
 __global__ __launch_bounds__(kBlock) void spmv_adaptive(const int2 *__restrict__ blk, const int *__restrict__ rp,
                                                         const int *__restrict__ ci, const double *__restrict__ v,
@@ -1127,53 +1153,25 @@ __global__ __launch_bounds__(kBlock) void spmv_adaptive(const int2 *__restrict__
                                                         const double *__restrict__ pv, const int2 *__restrict__ pb,
                                                         DevDict dt = DevDict())
 {
-    auto epi = [&](int r, double s) -> double {
-        double out;
-        if constexpr (OP == SSS_HIP_SPMV_MXY) out = s;
-        else if constexpr (OP == SSS_HIP_SPMV_AMXPY) out = y[r] + s * alpha;
-        else if constexpr (OP == SSS_HIP_SPMV_RESID) out = b[r] + s * alpha;
-        else {
-            if (cap > 0 && r >= cap) return 0.0;   // as-shipped <<<64,64>>> row cap
-            out = y[r] + s;
-        }
-        y[r] = out;
-        return NORM ? out * out : 0.0;
-    };
     if constexpr (DICT >= kXell) {   // column ELL rows of width DICT - kXell: one thread per row
         constexpr int W = DICT - kXell;
         __shared__ XellSmem es;
         const int bid = blockIdx.x;
-        unsigned w[W];
         double br = 0.0;
-        int r = 0;
-        bool live = false;
         const bool valid = bid < dt.bend;
-#pragma unroll
-        for (int t = 0; t < W; ++t) w[t] = 0xffffffffu;
-        if (valid) {   // codes (and b) in flight across the dictionary's barrier
-            const int2 ba = blk[bid], be = blk[bid + 1];
-            r = ba.x + (int)threadIdx.x;
-            live = r < be.x;
-            if (live) {
-                xell_codes<W>(dt.xell, r, w);
-                if constexpr (OP == SSS_HIP_SPMV_RESID) br = b[r];
-            }
-            xell_load_dict_nosync(dt, bid, es);
-        }
+        const XellRow<W> row = xell_row_begin<W>(valid, blk, bid, dt.xell, dt.pd, dt.vd, es, [&](int r) {
+            if constexpr (OP == SSS_HIP_SPMV_RESID) br = b[r];
+        });
+        const unsigned(&w)[W] = row.w;
+        const int r = row.r;
         __syncthreads();
         double sq = 0.0;
-        if (live) {
+        if (row.live) {
             double xv[W];
             int ds;
-            const int len = xell_gather<W>(w, r, dt.xshift, [&](int c) -> double { return x[c]; }, xv, ds);
-            const double sum = xell_add(0.0, w, xv, es, dt.xshift, 0, len);
-            if constexpr (OP == SSS_HIP_SPMV_RESID) {
-                const double out = br + sum * alpha;
-                y[r] = out;
-                sq = NORM ? out * out : 0.0;
-            } else {
-                sq = epi(r, sum);
-            }
+            unsigned dcode;
+            const int len = xell_gather<W>(w, r, dt.xshift, [&](int c) -> double { return x[c]; }, xv, ds, dcode);
+            sq = spmv_row_out<OP, NORM>(r, xell_sum_g<false>(0.0, w, xv, es, dt.xshift, 0, len), alpha, br, y, cap);
         }
         if (NORM && valid) {
             const double t = block_sum(sq, es.red);
@@ -1184,49 +1182,30 @@ __global__ __launch_bounds__(kBlock) void spmv_adaptive(const int2 *__restrict__
         constexpr int RPT = kEllRpt;
         __shared__ EllSmem es[RPT];
         const int g = (int)blockIdx.x;
-        unsigned w[RPT][W / 4];
+        EllRow<W> row[RPT];
         double br[RPT];
-        int r[RPT], rb[RPT];   // rb: the row's offset base (its own index, or dt.ellb[r])
-        bool live[RPT], valid[RPT];
+        int rb[RPT];   // the row's offset base (its own index, or dt.ellb[r])
 #pragma unroll
         for (int j = 0; j < RPT; ++j) {   // codes (and b) in flight across the dictionaries' barrier
-            const int bid = g * RPT + j;
-            valid[j] = bid < dt.bend;
-            live[j] = false;
             br[j] = 0.0;
-            r[j] = rb[j] = 0;
-#pragma unroll
-            for (int t = 0; t < W / 4; ++t) w[j][t] = 0u;
-            if (valid[j]) {
-                const int2 ba = blk[bid], be = blk[bid + 1];
-                r[j] = ba.x + (int)threadIdx.x;
-                live[j] = r[j] < be.x;
-                if (live[j]) {
-                    ell_codes<W>(dt.ell, r[j], w[j]);
-                    rb[j] = dt.ellb ? dt.ellb[r[j]] : r[j];
-                    if constexpr (OP == SSS_HIP_SPMV_RESID) br[j] = b[r[j]];
-                }
-                ell_load_dicts_nosync(dt, bid, es[j]);
-            }
+            rb[j] = 0;
+            row[j] = ell_row_begin<W>(blk, g * RPT + j, dt, es[j], [&](int r) {
+                rb[j] = dt.ellb ? dt.ellb[r] : r;
+                if constexpr (OP == SSS_HIP_SPMV_RESID) br[j] = b[r];
+            });
         }
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < RPT; ++j) {
             double sq = 0.0;
-            if (live[j]) {
+            if (row[j].live) {
                 double p[W];
                 int ds;
                 double dv;
-                const int len = ell_decode<W>(w[j], rb[j], es[j], [&](int c) -> double { return x[c]; }, p, ds, dv);
-                if constexpr (OP == SSS_HIP_SPMV_RESID) {
-                    const double out = br[j] + ell_add(0.0, p, 0, len) * alpha;
-                    y[r[j]] = out;
-                    sq = NORM ? out * out : 0.0;
-                } else {
-                    sq = epi(r[j], ell_add(0.0, p, 0, len));
-                }
+                const int len = ell_decode<W>(row[j].w, rb[j], es[j], [&](int c) -> double { return x[c]; }, p, ds, dv);
+                sq = spmv_row_out<OP, NORM>(row[j].r, ell_add(0.0, p, 0, len), alpha, br[j], y, cap);
             }
-            if (NORM && valid[j]) {
+            if (NORM && row[j].valid) {
                 const double t = block_sum(sq, es[j].red);
                 if (threadIdx.x == 0) partial[g * RPT + j] = t;
             }
@@ -1236,7 +1215,9 @@ __global__ __launch_bounds__(kBlock) void spmv_adaptive(const int2 *__restrict__
         __shared__ std::conditional_t<DICT != 0, DictSmem, char> dsm;
         DictSmem *ds = nullptr;
         if constexpr (DICT != 0) ds = &dsm;
-        const double sq = csr_block_rows(blk, rp, ci, v, x, sm, epi, pk, pv, pb, &dt, ds);
+        const double sq = csr_block_rows(
+            blk, rp, ci, v, x, sm, [&](int r, double s) -> double { return spmv_row_out<OP, NORM>(r, s, alpha, b, y, cap); },
+            pk, pv, pb, &dt, ds);
         if (NORM) {
             const double t = block_sum(sq, sm.red);
             if (threadIdx.x == 0) partial[xcd_bid()] = t;
@@ -1261,19 +1242,7 @@ __global__ __launch_bounds__(kBlock) void spmv_wave(int n, const int *__restrict
         auto prod = [&](int c, double a) { return a * x[c]; };
         const double s = TREE ? wave_row_sum(rp[r], rp[r + 1], ci, v, prod)
                               : wave_row_chain<false>(rp[r], rp[r + 1], ci, v, prod, 0.0, strips[TREE ? 0 : wave]);
-        if (lane == 0) {
-            bool write = true;
-            double out;
-            if constexpr (OP == SSS_HIP_SPMV_MXY) out = s;
-            else if constexpr (OP == SSS_HIP_SPMV_AMXPY) out = y[r] + s * alpha;
-            else if constexpr (OP == SSS_HIP_SPMV_RESID) out = b[r] + s * alpha;
-            else {
-                write = !(cap > 0 && r >= cap);
-                out = write ? y[r] + s : 0.0;
-            }
-            if (write) y[r] = out;
-            if (NORM) sq = out * out;
-        }
+        if (lane == 0) sq = spmv_row_out<OP, NORM>(r, s, alpha, b, y, cap);
     }
     if (NORM) {
         const double t = block_sum(sq, red);
@@ -1298,19 +1267,7 @@ __global__ __launch_bounds__(kBlock) void spmv_merged(int n, int ng, int W, cons
     if (merged_block<G, 1, LDSACC>(gp, ng, W, mk, mv, [&](int c) -> double { return x[c]; }, red, acc, g, u, sr,
                                    unused)) {
         const int r = g * G + u;
-        if (r < n) {
-            bool write = true;
-            double out;
-            if constexpr (OP == SSS_HIP_SPMV_MXY) out = sr;
-            else if constexpr (OP == SSS_HIP_SPMV_AMXPY) out = y[r] + sr * alpha;
-            else if constexpr (OP == SSS_HIP_SPMV_RESID) out = b[r] + sr * alpha;
-            else {
-                write = !(cap > 0 && r >= cap);
-                out = write ? y[r] + sr : 0.0;
-            }
-            if (write) y[r] = out;
-            if (NORM) sq = out * out;
-        }
+        if (r < n) sq = spmv_row_out<OP, NORM>(r, sr, alpha, b, y, cap);
     }
     if (NORM) {
         const double t = block_sum(sq, nred);
@@ -1322,19 +1279,13 @@ template <int OP, bool NORM>
 static void launch_op(const DevCSR &A, double alpha, const double *x, const double *b, double *y, int cap,
                       double *partial, hipStream_t s)
 {
-    if (A.mg_G == 8 && A.mg_acc)
-        hipLaunchKernelGGL((spmv_merged<OP, NORM, 8, true>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
-                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
-    else if (A.mg_G == 8)
-        hipLaunchKernelGGL((spmv_merged<OP, NORM, 8>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
-                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
-    else if (A.mg_G == 4 && A.mg_acc)
-        hipLaunchKernelGGL((spmv_merged<OP, NORM, 4, true>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
-                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
-    else if (A.mg_G == 4)
-        hipLaunchKernelGGL((spmv_merged<OP, NORM, 4>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W,
-                           A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap, partial);
-    else if (A.vec_rows)
+    if (with_merged_kind(A, [&](auto G, auto ACC) {
+            hipLaunchKernelGGL((spmv_merged<OP, NORM, decltype(G)::value, decltype(ACC)::value>), dim3(A.ngrid),
+                               dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W, A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap,
+                               partial);
+        }))
+        return;
+    if (A.vec_rows)
         hipLaunchKernelGGL((spmv_wave<OP, NORM, true>), dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.rp, A.ci, A.v, x,
                            b, y, alpha, cap, partial);
     else if (A.wave_rows)
@@ -1355,21 +1306,34 @@ static void launch_op(const DevCSR &A, double alpha, const double *x, const doub
 // and write y)
 static double spmv_row_bytes(int op) { return op == SSS_HIP_SPMV_MXY ? 8.0 : 16.0; }
 
+// f(std::integral_constant<int, OP>, std::bool_constant<NORM>) for a run-time op; NORM (per-block sums
+// of squares into `partial`) exists for RESID only.  False, f not called, for an unknown op.
+template <class F>
+static bool with_spmv_op(int op, bool partial, F f)
+{
+    switch (op) {
+    case SSS_HIP_SPMV_MXY: f(std::integral_constant<int, SSS_HIP_SPMV_MXY>(), std::false_type()); break;
+    case SSS_HIP_SPMV_AMXPY: f(std::integral_constant<int, SSS_HIP_SPMV_AMXPY>(), std::false_type()); break;
+    case SSS_HIP_SPMV_RESID:
+        if (partial) f(std::integral_constant<int, SSS_HIP_SPMV_RESID>(), std::true_type());
+        else f(std::integral_constant<int, SSS_HIP_SPMV_RESID>(), std::false_type());
+        break;
+    case SSS_HIP_SPMV_ACC: f(std::integral_constant<int, SSS_HIP_SPMV_ACC>(), std::false_type()); break;
+    default: return false;
+    }
+    return true;
+}
+
 int launch_spmv(const DevCSR &A, int op, double alpha, const double *x, const double *b, double *y, int cap,
                 double *partial, hipStream_t stream)
 {
     if (A.n == 0 || A.nblk == 0) return 0;
     if (ledger_on()) ledger_add(matrix_bytes(A, 0, A.nblk) + xgather_bytes(A, A.n) + spmv_row_bytes(op) * A.n);
-    switch (op) {
-    case SSS_HIP_SPMV_MXY: launch_op<SSS_HIP_SPMV_MXY, false>(A, alpha, x, b, y, cap, nullptr, stream); break;
-    case SSS_HIP_SPMV_AMXPY: launch_op<SSS_HIP_SPMV_AMXPY, false>(A, alpha, x, b, y, cap, nullptr, stream); break;
-    case SSS_HIP_SPMV_RESID:
-        if (partial) launch_op<SSS_HIP_SPMV_RESID, true>(A, alpha, x, b, y, cap, partial, stream);
-        else launch_op<SSS_HIP_SPMV_RESID, false>(A, alpha, x, b, y, cap, nullptr, stream);
-        break;
-    case SSS_HIP_SPMV_ACC: launch_op<SSS_HIP_SPMV_ACC, false>(A, alpha, x, b, y, cap, nullptr, stream); break;
-    default: return ERROR_INPUT_PAR;
-    }
+    if (!with_spmv_op(op, partial != nullptr, [&](auto O, auto NM) {
+            launch_op<decltype(O)::value, decltype(NM)::value>(A, alpha, x, b, y, cap,
+                                                               decltype(NM)::value ? partial : nullptr, stream);
+        }))
+        return ERROR_INPUT_PAR;
     SSS_HIP(hipGetLastError());
     return 0;
 }
@@ -1401,6 +1365,8 @@ int launch_spmv_range(const DevCSR &A, int blo, int bhi, int op, double alpha, c
                       double *y, double *partial, hipStream_t s)
 {
     if (A.wave_rows || A.vec_rows || blo < 0 || bhi > A.nblk) return ERROR_INPUT_PAR;
+    // (ACC, whose row cap has no meaning on a block range, and unknown ops: refused before anything is
+    // counted or launched, so with_spmv_op below always finds the op)
     if (op != SSS_HIP_SPMV_RESID && op != SSS_HIP_SPMV_AMXPY && op != SSS_HIP_SPMV_MXY) return ERROR_INPUT_PAR;
     const int nb = bhi - blo;
     if (nb <= 0) return 0;
@@ -1413,7 +1379,7 @@ int launch_spmv_range(const DevCSR &A, int blo, int bhi, int op, double alpha, c
     double *pp = partial ? partial + blo : nullptr;
     DevDict dt = devdict(A, blo);
     dt.bend = nb;   // the kernel sees blocks [0, nb)
-    auto go = [&](auto op_c, auto norm_c) {
+    with_spmv_op(op, partial != nullptr, [&](auto op_c, auto norm_c) {
         constexpr int O = decltype(op_c)::value;
         constexpr bool NM = decltype(norm_c)::value;
         with_tile_kind(A, [&](auto K) {
@@ -1422,13 +1388,7 @@ int launch_spmv_range(const DevCSR &A, int blo, int bhi, int op, double alpha, c
             hipLaunchKernelGGL((spmv_adaptive<O, NM, KK>), dim3(grid), dim3(kBlock), 0, s, A.bk + blo, A.rp, A.ci, A.v,
                                x, b, y, alpha, 0, pp, A.pk, A.pv, pb, dt);
         });
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    if (op == SSS_HIP_SPMV_AMXPY) go(std::integral_constant<int, SSS_HIP_SPMV_AMXPY>(), F());
-    else if (op == SSS_HIP_SPMV_MXY) go(std::integral_constant<int, SSS_HIP_SPMV_MXY>(), F());
-    else if (partial) go(std::integral_constant<int, SSS_HIP_SPMV_RESID>(), T());
-    else go(std::integral_constant<int, SSS_HIP_SPMV_RESID>(), F());
+    });
     SSS_HIP(hipGetLastError());
     return 0;
 }

@@ -86,6 +86,36 @@ __device__ __forceinline__ void ell_codes(const unsigned char *__restrict__ ell,
         }
     }
 }
+// The prologue of the dictionary-ELL kernels, one thread per row of block `bid` (valid: the block
+// is inside the launch's range; uniform over the workgroup): the row's codes (0 for a thread without
+// a row), whatever early(r) loads for the row and the block's dictionaries all issued here, in
+// flight across the barrier the caller places after the last of its blocks.
+template <int W>
+struct EllRow {
+    unsigned w[W / 4];
+    int r = 0;
+    bool live = false, valid = false;
+};
+template <int W, class Early>
+__device__ __forceinline__ EllRow<W> ell_row_begin(const int2 *__restrict__ blk, int bid, const DevDict &dt, EllSmem &es,
+                                                   Early early)
+{
+    EllRow<W> t;
+    t.valid = bid < dt.bend;
+#pragma unroll
+    for (int s = 0; s < W / 4; ++s) t.w[s] = 0u;
+    if (t.valid) {
+        const int2 ba = blk[bid], be = blk[bid + 1];
+        t.r = ba.x + (int)threadIdx.x;
+        t.live = t.r < be.x;
+        if (t.live) {
+            ell_codes<W>(dt.ell, t.r, t.w);
+            early(t.r);
+        }
+        ell_load_dicts_nosync(dt, bid, es);
+    }
+    return t;
+}
 // Products of row r in stored (slot) order from its codes: p[s] = a_s * x(c_s) for s < len;
 // dslot = the row's (last) diagonal slot or -1, dval its value.  DIAG = false: the caller never
 // reads p[dslot] (a relaxation pass subtracts every other product), so x_r is not fetched for it
@@ -212,10 +242,11 @@ struct XellSmem {
     double vd[kXellValues];
     double red[kBlock / 64];
 };
-__device__ __forceinline__ void xell_load_dict_nosync(const DevDict &dt, int bid, XellSmem &es)
+__device__ __forceinline__ void xell_load_dict_nosync(const int4 *__restrict__ pd, const double *__restrict__ vd, int bid,
+                                                      XellSmem &es)
 {
-    const int4 p = dt.pd[bid];
-    for (int t = threadIdx.x; t < p.w; t += kBlock) es.vd[t] = dt.vd[p.z + t];
+    const int4 p = pd[bid];
+    for (int t = threadIdx.x; t < p.w; t += kBlock) es.vd[t] = vd[p.z + t];
 }
 template <int W>
 __device__ __forceinline__ void xell_codes(const unsigned *__restrict__ xell, int r, unsigned (&w)[W])
@@ -227,6 +258,36 @@ __device__ __forceinline__ void xell_codes(const unsigned *__restrict__ xell, in
         const uint4 u = q[h];
         w[4 * h] = u.x, w[4 * h + 1] = u.y, w[4 * h + 2] = u.z, w[4 * h + 3] = u.w;
     }
+}
+// The prologue of every column-ELL kernel, one thread per row of block `bid` (valid: the block exists;
+// uniform over the workgroup): the row's codes (pads for a thread without a row), whatever early(r)
+// loads for the row (b, a divisor, ...) and the block's dictionary all issued here, in flight across
+// the barrier the caller places after it.
+template <int W>
+struct XellRow {
+    unsigned w[W];
+    int r = 0;
+    bool live = false;
+};
+template <int W, class Early>
+__device__ __forceinline__ XellRow<W> xell_row_begin(bool valid, const int2 *__restrict__ blk, int bid,
+                                                     const unsigned *__restrict__ xell, const int4 *__restrict__ pd,
+                                                     const double *__restrict__ vd, XellSmem &es, Early early)
+{
+    XellRow<W> t;
+#pragma unroll
+    for (int s = 0; s < W; ++s) t.w[s] = 0xffffffffu;
+    if (valid) {
+        const int2 ba = blk[bid], be = blk[bid + 1];
+        t.r = ba.x + (int)threadIdx.x;
+        t.live = t.r < be.x;
+        if (t.live) {
+            xell_codes<W>(xell, t.r, t.w);
+            early(t.r);
+        }
+        xell_load_dict_nosync(pd, vd, bid, es);
+    }
+    return t;
 }
 // Row r's x values in slot order, xv[s] = x(c_s) for s < len (0.0 past it); dslot = the row's
 // (last) diagonal slot or -1 (DIAG = false: xv[dslot] = 0 without a fetch, as ell_decode).  The products a_s * xv[s] are formed where they are summed
@@ -250,17 +311,10 @@ __device__ __forceinline__ int xell_gather(const unsigned (&w)[W], int r, int sh
     for (int s = 0; s < W; ++s) xv[s] = (s < len && (DIAG || s != dslot)) ? fetch((int)(w[s] & mask)) : 0.0;
     return len;
 }
-template <int W, bool DIAG = true, class Fetch>
-__device__ __forceinline__ int xell_gather(const unsigned (&w)[W], int r, int shift, Fetch fetch, double (&xv)[W],
-                                           int &dslot)
-{
-    unsigned dcode;
-    return xell_gather<W, DIAG>(w, r, shift, fetch, xv, dslot, dcode);
-}
 // s0 + (or -) the products a_s * xv[s] of slots [a, e) in slot order, a_s = the block's value of slot
 // s (LDS).  Branch-free form: every slot's LDS value is read first (slots outside [a, e) read entry 0)
-// and each step is a select.  It holds W more doubles live than the per-slot form (xell_add /
-// xell_sub): measured at 400^3 the two-stage stage-0 kernel ran 4 % faster with it, the level-1
+// and each step is a select.  It holds W more doubles live than the per-slot form (xell_sum_g):
+// measured at 400^3 the two-stage stage-0 kernel ran 4 % faster with it, the level-1
 // relaxation (122 VGPRs instead of 70: 4 waves per SIMD instead of 7) 3 % slower, so only the former uses it.
 template <bool SUB, int W>
 __device__ __forceinline__ double xell_sum_bf(double s0, const unsigned (&w)[W], const double (&xv)[W], const XellSmem &es,
@@ -288,65 +342,46 @@ __device__ __forceinline__ double xell_sum_g(double s0, const unsigned (&w)[W], 
         if (s >= a && s < e) s0 = SUB ? s0 - es.vd[w[s] >> shift] * xv[s] : s0 + es.vd[w[s] >> shift] * xv[s];
     return s0;
 }
-template <int W>
-__device__ __forceinline__ double xell_add(double s0, const unsigned (&w)[W], const double (&xv)[W], const XellSmem &es,
-                                           int shift, int a, int e)
-{
-    return xell_sum_g<false>(s0, w, xv, es, shift, a, e);
-}
-template <int W>
-__device__ __forceinline__ double xell_sub(double s0, const unsigned (&w)[W], const double (&xv)[W], const XellSmem &es,
-                                           int shift, int a, int e)
-{
-    return xell_sum_g<true>(s0, w, xv, es, shift, a, e);
-}
 
-// sum of p[a, e) from s0 in slot order (branch-free: a select per slot)
-template <int W>
-__device__ __forceinline__ double ell_add(double s0, const double (&p)[W], int a, int e)
+// s0 + (SUB: -) p[a, e) in slot order (branch-free: a select per slot)
+template <bool SUB, int W>
+__device__ __forceinline__ double ell_sum(double s0, const double (&p)[W], int a, int e)
 {
 #pragma unroll
     for (int s = 0; s < W; ++s) {
-        const double t = s0 + p[s];
+        const double t = SUB ? s0 - p[s] : s0 + p[s];
         s0 = (s >= a && s < e) ? t : s0;
     }
     return s0;
 }
 template <int W>
-__device__ __forceinline__ double ell_sub(double s0, const double (&p)[W], int a, int e)
-{
-#pragma unroll
-    for (int s = 0; s < W; ++s) {
-        const double t = s0 - p[s];
-        s0 = (s >= a && s < e) ? t : s0;
-    }
-    return s0;
-}
+__device__ __forceinline__ double ell_add(double s0, const double (&p)[W], int a, int e) { return ell_sum<false>(s0, p, a, e); }
+template <int W>
+__device__ __forceinline__ double ell_sub(double s0, const double (&p)[W], int a, int e) { return ell_sum<true>(s0, p, a, e); }
 
 // In-order chains over LDS products: 8 reads issued ahead of 8 dependent adds/subtractions,
 // the additions themselves in exactly the stored order.
-__device__ __forceinline__ double chain_add(double s, const double *p, int a, int e)
+template <bool SUB>
+__device__ __forceinline__ double chain_sum(double s, const double *p, int a, int e)
 {
     int k = a;
     for (; k + 8 <= e; k += 8) {
         const double p0 = p[k], p1 = p[k + 1], p2 = p[k + 2], p3 = p[k + 3];
         const double p4 = p[k + 4], p5 = p[k + 5], p6 = p[k + 6], p7 = p[k + 7];
-        s += p0; s += p1; s += p2; s += p3; s += p4; s += p5; s += p6; s += p7;
+        s = SUB ? s - p0 : s + p0;
+        s = SUB ? s - p1 : s + p1;
+        s = SUB ? s - p2 : s + p2;
+        s = SUB ? s - p3 : s + p3;
+        s = SUB ? s - p4 : s + p4;
+        s = SUB ? s - p5 : s + p5;
+        s = SUB ? s - p6 : s + p6;
+        s = SUB ? s - p7 : s + p7;
     }
-    for (; k < e; ++k) s += p[k];
+    for (; k < e; ++k) s = SUB ? s - p[k] : s + p[k];
     return s;
 }
-__device__ __forceinline__ double chain_sub(double s, const double *p, int a, int e)
-{
-    int k = a;
-    for (; k + 8 <= e; k += 8) {
-        const double p0 = p[k], p1 = p[k + 1], p2 = p[k + 2], p3 = p[k + 3];
-        const double p4 = p[k + 4], p5 = p[k + 5], p6 = p[k + 6], p7 = p[k + 7];
-        s -= p0; s -= p1; s -= p2; s -= p3; s -= p4; s -= p5; s -= p6; s -= p7;
-    }
-    for (; k < e; ++k) s -= p[k];
-    return s;
-}
+__device__ __forceinline__ double chain_add(double s, const double *p, int a, int e) { return chain_sum<false>(s, p, a, e); }
+__device__ __forceinline__ double chain_sub(double s, const double *p, int a, int e) { return chain_sum<true>(s, p, a, e); }
 
 // The in-order chain with its schedule fixed: groups of G products read as 16-byte pairs into two
 // register sets in turn, each group's G dependent adds in one asm block, so the compiler neither
@@ -431,6 +466,9 @@ __device__ __forceinline__ double chain_pipe16(double s, const double *p, int a,
     return a < e ? chain_fixed<SUB, 16>(s, p + a, e - a) : s;
 }
 
+// The relaxations' divisor guard (Solve/SSS_smooth.c): a row whose divisor fails it keeps its value.
+__device__ __forceinline__ bool div_ok(double d) { return fabs(d) > SMALLFLOAT; }
+
 // Fixed-order block reduction (xor butterfly inside the wave, then waves in order).
 // Result valid in thread 0.  Must be reached by every thread of the block.
 __device__ __forceinline__ double block_sum(double v, double *red)
@@ -446,19 +484,6 @@ __device__ __forceinline__ double block_sum(double v, double *red)
     return t;
 }
 
-__device__ __forceinline__ double block_max(double v, double *red)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t = fmax(t, red[w]);
-    return t;
-}
-
 // Tree sum of the LDS products p[a, e) (thread-strided partial sums, block_sum): the free
 // summation order of a long row's chunk (DevCSR::tree_long).  Result valid in thread 0; every
 // thread of the block must call it.
@@ -469,95 +494,73 @@ __device__ __forceinline__ double block_tree_sum(const double *p, int a, int e, 
     return block_sum(t, red);
 }
 
-// Phase 1 of every tile kernel: sm[k - k0] = v[k] * x[ci[k]] for k in [k0, k1).  Each thread
-// issues all its column/value loads of a batch first, then all its x gathers, so up to 8 + 8
-// independent loads per thread are in flight (2x the bandwidth of the load-multiply loop on a
-// 7-point operator).  A negative column (diagonal sentinel of the relaxation copies) stores an
-// exact +0.0.
-__device__ __forceinline__ void stage_products(double *__restrict__ sm, int k0, int k1, const int *__restrict__ ci,
-                                               const double *__restrict__ v, const double *x)
+// Phase 1 of every tile kernel: sm[k - k0] = v[k] * fetch(ci[k]) for k in [k0, k1), by NT threads
+// (this one is thread `t` of them).  Each thread issues all its column/value loads of a batch first,
+// then all its x gathers, so up to 8 + 8 independent loads per thread are in flight (2x the
+// bandwidth of the load-multiply loop on a 7-point operator).  SENT: a negative column (diagonal
+// sentinel of the relaxation copies) is not fetched and stores an exact +0.0.
+template <bool SENT, int NT, class Fetch>
+__device__ __forceinline__ void stage_loop(double *__restrict__ sm, int k0, int k1, const int *__restrict__ ci,
+                                           const double *__restrict__ v, Fetch fetch, int t)
 {
     constexpr int U = 8;
-    for (int kb = k0 + (int)threadIdx.x; kb < k1; kb += U * kBlock) {
-        int j[U];
-        double a[U], xv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = kb + u * kBlock;
-            j[u] = k < k1 ? ci[k] : -1;
-            a[u] = k < k1 ? v[k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[u] = j[u] >= 0 ? x[j[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = kb + u * kBlock;
-            if (k < k1) sm[k - k0] = j[u] >= 0 ? a[u] * xv[u] : 0.0;
-        }
-    }
-}
-
-// As stage_products, by `nt` threads of the block (this one is thread `t` of them).
-__device__ __forceinline__ void stage_products_part(double *__restrict__ sm, int k0, int k1,
-                                                    const int *__restrict__ ci, const double *__restrict__ v,
-                                                    const double *x, int t, int nt)
-{
-    constexpr int U = 8;
-    for (int kb = k0 + t; kb < k1; kb += U * nt) {
-        int j[U];
-        double a[U], xv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = kb + u * nt;
-            j[u] = k < k1 ? ci[k] : -1;
-            a[u] = k < k1 ? v[k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[u] = j[u] >= 0 ? x[j[u]] : 0.0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int k = kb + u * nt;
-            if (k < k1) sm[k - k0] = j[u] >= 0 ? a[u] * xv[u] : 0.0;
-        }
-    }
-}
-
-// As stage_products, with the x value of each (possibly encoded) column supplied by `fetch`.
-template <class Fetch>
-__device__ __forceinline__ void stage_products_f(double *__restrict__ sm, int k0, int k1, const int *__restrict__ ci,
-                                                 const double *__restrict__ v, Fetch fetch)
-{
-    constexpr int U = 8;
-    for (int kb = k0 + (int)threadIdx.x; kb < k1; kb += U * kBlock) {
+    for (int kb = k0 + t; kb < k1; kb += U * NT) {
         int c[U];
         double a[U], xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = kb + u * kBlock;
-            c[u] = k < k1 ? ci[k] : 0;
+            const int k = kb + u * NT;
+            c[u] = k < k1 ? ci[k] : (SENT ? -1 : 0);
             a[u] = k < k1 ? v[k] : 0.0;
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) xv[u] = kb + u * kBlock < k1 ? fetch(c[u]) : 0.0;
+        for (int u = 0; u < U; ++u) xv[u] = (SENT ? c[u] >= 0 : kb + u * NT < k1) ? fetch(c[u]) : 0.0;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int k = kb + u * kBlock;
-            if (k < k1) sm[k - k0] = a[u] * xv[u];
+            const int k = kb + u * NT;
+            if (k < k1) sm[k - k0] = (!SENT || c[u] >= 0) ? a[u] * xv[u] : 0.0;
         }
     }
+}
+// The two forwarding names below carry no __restrict__ of their own (stage_loop has the qualifiers):
+// with it a second set of no-alias scopes took relax_range_occ<0, 0> from 70 to 76 VGPRs and from 7
+// to 6 waves per SIMD.
+// by the whole block, x read directly (columns may be the sentinel)
+__device__ __forceinline__ void stage_products(double *sm, int k0, int k1, const int *ci, const double *v, const double *x)
+{
+    stage_loop<true, kBlock>(sm, k0, k1, ci, v, [&](int c) -> double { return x[c]; }, (int)threadIdx.x);
+}
+// by the whole block, the x value of each (possibly encoded) column supplied by `fetch`
+template <class Fetch>
+__device__ __forceinline__ void stage_products_f(double *sm, int k0, int k1, const int *ci, const double *v, Fetch fetch)
+{
+    stage_loop<false, kBlock>(sm, k0, k1, ci, v, fetch, (int)threadIdx.x);
 }
 
 // Column-sorted staging (DevCSR::pk/pv/pb): slot k of the segment [k0, k1) holds the entry packed
 // as cluster << 31 | (col - base[cluster]) << kTileShift | pos, pos = its stored-order position in
 // the segment (a diagonal entry: offset kTileDiagMark + its row in the block); the product goes to
 // sm[pos], so the LDS image is exactly stage_products_f's and every chain over it is unchanged.
+// a slot's column-offset field, and its column (diagonal marks: the row itself)
+__device__ __forceinline__ unsigned slot_off(unsigned q) { return (q >> kTileShift) & ((1u << kTileColBits) - 1); }
+__device__ __forceinline__ int slot_col(unsigned q, int2 base, int r0)
+{
+    const unsigned off = slot_off(q);
+    return off >= kTileDiagMark ? r0 + (int)(off - kTileDiagMark) : (int)off + ((q >> 31) ? base.y : base.x);
+}
+// the slot's product to its stored-order position; a diagonal slot's value to diag[its row], if given
+__device__ __forceinline__ void slot_store(double *sm, double *diag, unsigned q, double a, double xv)
+{
+    sm[q & (kTileEntries - 1)] = a * xv;
+    const unsigned off = slot_off(q);
+    if (diag && off >= kTileDiagMark) diag[off - kTileDiagMark] = a;
+}
 template <class Fetch>
 __device__ __forceinline__ void stage_sorted(double *__restrict__ sm, int k0, int k1, const unsigned *__restrict__ pk,
                                              const double *__restrict__ pv, int2 base, int r0, double *diag,
                                              Fetch fetch)
 {
     constexpr int U = 8;
-    constexpr unsigned kMask = kTileEntries - 1;
     for (int kb = k0 + (int)threadIdx.x; kb < k1; kb += U * kBlock) {
         unsigned q[U];
         double a[U], xv[U];
@@ -568,18 +571,10 @@ __device__ __forceinline__ void stage_sorted(double *__restrict__ sm, int k0, in
             a[u] = k < k1 ? pv[k] : 0.0;
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned off = (q[u] >> kTileShift) & ((1u << kTileColBits) - 1);
-            const int c = off >= kTileDiagMark ? r0 + (int)(off - kTileDiagMark) : (int)off + ((q[u] >> 31) ? base.y : base.x);
-            xv[u] = kb + u * kBlock < k1 ? fetch(c) : 0.0;
-        }
+        for (int u = 0; u < U; ++u) xv[u] = kb + u * kBlock < k1 ? fetch(slot_col(q[u], base, r0)) : 0.0;
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (kb + u * kBlock < k1) {
-                sm[q[u] & kMask] = a[u] * xv[u];
-                const unsigned off = (q[u] >> kTileShift) & ((1u << kTileColBits) - 1);
-                if (diag && off >= kTileDiagMark) diag[off - kTileDiagMark] = a[u];
-            }
+            if (kb + u * kBlock < k1) slot_store(sm, diag, q[u], a[u], xv[u]);
     }
 }
 
@@ -606,7 +601,6 @@ __device__ __forceinline__ void stage_vdict(double *__restrict__ sm, int k0, int
                                             const unsigned (*pre_w)[kVdictU] = nullptr)
 {
     constexpr int U = kVdictU;
-    constexpr unsigned kMask = kTileEntries - 1;
     for (int kb = k0 + (int)threadIdx.x; kb < k1; kb += U * kBlock) {
         unsigned q[U], w[U];
         double a[U], xv[U];
@@ -618,18 +612,12 @@ __device__ __forceinline__ void stage_vdict(double *__restrict__ sm, int k0, int
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const unsigned off = (q[u] >> kTileShift) & ((1u << kTileColBits) - 1);
-            const int c = off >= kTileDiagMark ? r0 + (int)(off - kTileDiagMark) : (int)off + ((q[u] >> 31) ? base.y : base.x);
-            xv[u] = kb + u * kBlock < k1 ? fetch(c) : 0.0;
+            xv[u] = kb + u * kBlock < k1 ? fetch(slot_col(q[u], base, r0)) : 0.0;
             a[u] = vd[w[u]];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (kb + u * kBlock < k1) {
-                sm[q[u] & kMask] = a[u] * xv[u];
-                const unsigned off = (q[u] >> kTileShift) & ((1u << kTileColBits) - 1);
-                if (diag && off >= kTileDiagMark) diag[off - kTileDiagMark] = a[u];
-            }
+            if (kb + u * kBlock < k1) slot_store(sm, diag, q[u], a[u], xv[u]);
     }
 }
 
@@ -719,11 +707,6 @@ __device__ __forceinline__ void stage_any(double *__restrict__ sm, int k0, int k
     else stage_any(sm, k0, k1, ci, v, pk, pv, pb, bid, r0, diag, fetch);
 }
 
-// Returns this thread's summed epilogue contribution (0 for idle threads).
-// Phase 1: every thread of the workgroup forms products of the tile (coalesced val/col loads,
-// independent x gathers, all in flight).  Phase 2: one thread per row adds its products from
-// LDS in stored order starting from 0.0 (SSS_utils.c:174).  Rows longer than the tile are
-// processed alone, tile by tile, with thread 0 carrying the chain.
 // A block's row and entry bounds: from {row, entry} pairs (one load each side) or from the
 // first-row array through row_ptr.
 struct BlockBounds {
@@ -740,6 +723,29 @@ __device__ __forceinline__ BlockBounds block_bounds(const int *__restrict__ blk,
     return {r0, r1, rp[r0], rp[r1]};
 }
 
+// One long row (a block of its own), chunk by chunk: stage(base, m) puts the products of its entries
+// [base, base + m) into LDS, then acc = act(base, m, acc) takes them into the row's running value --
+// thread 0's chain (whole, with a hole at the diagonal, or cut at a split point) or a tree sum by the
+// block.  Both are called by every thread of the block, with a barrier after each; the row's value
+// is thread 0's.
+template <class Stage, class Act>
+__device__ __forceinline__ double long_row_chunks(int k0, int k1, double acc, Stage stage, Act act)
+{
+    for (int base = k0; base < k1; base += kTileEntries) {
+        const int m = min(kTileEntries, k1 - base);
+        stage(base, m);
+        __syncthreads();
+        acc = act(base, m, acc);
+        __syncthreads();
+    }
+    return acc;
+}
+
+// Returns this thread's summed epilogue contribution (0 for idle threads).
+// Phase 1: every thread of the workgroup forms products of the tile (coalesced val/col loads,
+// independent x gathers, all in flight).  Phase 2: one thread per row adds its products from
+// LDS in stored order starting from 0.0 (SSS_utils.c:174).  Rows longer than the tile are
+// processed alone, tile by tile, with thread 0 carrying the chain.
 template <class Epi, class BlkT>
 __device__ __forceinline__ double csr_block_rows(const BlkT *__restrict__ blk, const int *__restrict__ rp,
                                                  const int *__restrict__ ci, const double *__restrict__ v,
@@ -781,11 +787,13 @@ __device__ __forceinline__ double csr_block_rows(const BlkT *__restrict__ blk, c
             double *cur = sm.v + (c & 1) * H, *nxt = sm.v + ((c + 1) & 1) * H;
             if (threadIdx.x == 0) s = chain_pipe16<false>(s, cur, 0, m);
             else if (threadIdx.x >= 64 && nb < k1)
-                stage_products_part(nxt, nb, min(nb + H, k1), ci, v, x, (int)threadIdx.x - 64, kBlock - 64);
+                stage_loop<true, kBlock - 64>(nxt, nb, min(nb + H, k1), ci, v, fetch, (int)threadIdx.x - 64);
             __syncthreads();
         }
         if (threadIdx.x == 0) contrib = epi(r0, s);
     } else {
+        // (the chunk loop written out: as long_row_chunks' callables the dictionary-tile SpMV kernels
+        // compiled to two more scalar-register spills)
         double s = 0.0;
         for (int base = k0; base < k1; base += kTileEntries) {
             const int m = min(kTileEntries, k1 - base);
@@ -805,12 +813,6 @@ __device__ __forceinline__ double csr_block_rows(const BlkT *__restrict__ blk, c
     }
     return contrib;
 }
-
-
-
-}  // namespace sss
-
-namespace sss {
 
 // Relaxation rows over a row-compacted CSR (one smoother class): local row r is global row
 // map[r]; diagonal entries carry column -1 (set at upload) so their product is +0.0, an exact
@@ -838,24 +840,12 @@ __device__ __forceinline__ void csr_block_relax(const int *__restrict__ blk, con
         }
     } else {
         const int i = map[r0];
-        double acc = b[i];
-        for (int base = k0; base < k1; base += kTileEntries) {
-            const int m = min(kTileEntries, k1 - base);
-            stage_products(sm.v, base, base + m, ci, v, x);
-            __syncthreads();
-            if (threadIdx.x == 0) acc = chain_sub(acc, sm.v, 0, m);
-            __syncthreads();
-        }
+        const double acc = long_row_chunks(
+            k0, k1, b[i], [=, &sm](int base, int m) { stage_products(sm.v, base, base + m, ci, v, x); },
+            [&sm](int, int m, double acc) { return threadIdx.x == 0 ? chain_sub(acc, sm.v, 0, m) : acc; });
         if (threadIdx.x == 0) epi(r0, i, acc);
     }
 }
-
-
-
-}  // namespace sss
-
-namespace sss {
-
 // ---- wave-per-row path for long rows (avg nnz/row >= kWaveRowMin) ----------------------------
 // Four rows per 256-thread workgroup, one per wave.  All 64 lanes gather a strip of the row's
 // products (kWaveStage / 64 independent loads per lane) into the wave's private LDS strip; lane 0

@@ -528,6 +528,79 @@ def test_relabeled_level_smoothers_bitwise(request, hname, smoother, inner, row_
         D.close()
 
 
+def _banded_csr(n, noff, nodiag_every=97):
+    """A symmetric banded M-matrix: 2 * noff off-diagonals (offsets 1, 3, 6, 10, ... each way, three
+    distinct values), a constant dominant diagonal that every `nodiag_every`-th row lacks."""
+    offs = [k * (k + 1) // 2 for k in range(1, noff + 1)]
+    vals = {o: -(1.0 + 0.25 * (k % 3)) for k, o in enumerate(offs)}
+    diag = 1.0 + 2.0 * sum(-v for v in vals.values())
+    rp, ci, v = [0], [], []
+    for i in range(n):
+        row = [(i - o, vals[o]) for o in reversed(offs) if i - o >= 0]
+        if i % nodiag_every != 5:
+            row.append((i, diag))
+        row += [(i + o, vals[o]) for o in offs if i + o < n]
+        ci += [c for c, _ in row]
+        v += [a for _, a in row]
+        rp.append(len(ci))
+    return A.NumpyCSR(rp, ci, v)
+
+
+@pytest.mark.parametrize("noff,width", [(7, 16), (11, 24)])
+def test_banded_ell_widths_bitwise(quiet, monkeypatch, noff, width):
+    """The ELL row widths the stencil hierarchies do not produce.  600 rows (three 256-row blocks, the
+    last partial), 2 * noff + 1 entries per row, the diagonal missing on a few rows.  Unrelabeled, with
+    15 offsets and 4 values, the matrix is a dictionary ELL of width 16 to the SpMV (all four ops);
+    as level 0 of a hierarchy, relabeled (its offsets no longer fit a 1-byte dictionary), it is a
+    column ELL of width 16 or 24 to the C/F-Jacobi pass and, as [N | L] split copies, to the two-stage
+    kernels.  Everything bitwise the oracle."""
+    n = 600
+    M = _banded_csr(n, noff)
+    ora = oracle.load()
+    rng = np.random.default_rng(31)
+    monkeypatch.setenv("SSS_HIP_FORMATS", "full")
+    if width == 16:
+        for op in ("mxy", "amxpy", "resid", "acc"):
+            x, b, y0 = rng.standard_normal(n), rng.standard_normal(n), rng.standard_normal(n)
+            y_gpu, y_ref = y0.copy(), y0.copy()
+            alpha = -1.0 if op in ("resid", "amxpy") else 1.0
+            cap = 100 if op == "acc" else 0
+            assert _lib().sss_hip_host_spmv(A.SPMV[op], alpha, C.byref(M.mat), dptr(x), dptr(b), dptr(y_gpu), cap) == 0
+            if op == "mxy":
+                ora.ora_mv_mxy(C.byref(M.mat), dptr(x), dptr(y_ref))
+            elif op == "amxpy":
+                ora.ora_mv_amxpy(alpha, C.byref(M.mat), dptr(x), dptr(y_ref), 0)
+            elif op == "resid":
+                y_ref[:] = b
+                ora.ora_mv_amxpy(-1.0, C.byref(M.mat), dptr(x), dptr(y_ref), 0)
+            else:
+                ora.ora_mv_acc(C.byref(M.mat), dptr(x), dptr(y_ref), cap)
+            assert np.array_equal(y_gpu.view(np.uint64), y_ref.view(np.uint64)), op
+    H = build_hierarchy(M.mat, quiet)
+    L = H.level(0)
+    assert H.num_levels >= 2 and L.A.num_rows == n
+    for inner in (0, 1):
+        D = A.DeviceHierarchy(H, smoother="jacobi", coarse="direct", relabel=1, inner=inner, inner_from=0)
+        try:
+            assert D.level_info(0).a_format & 128, D.level_info(0).a_format   # column ELL
+            for post in (False, True):
+                b = rng.standard_normal(n)
+                x0 = rng.standard_normal(n)
+                D.upload(0, "b", b)
+                D.upload(0, "x", x0)
+                D.smooth(0, post)
+                xg = D.download(0, "x")
+                xr = x0.copy()
+                sweeps = H.pars.post_iter if post else H.pars.pre_iter
+                if inner > 0:
+                    ora.ora_cf_twostage(dptr(xr), C.byref(L.A), dptr(b), sweeps, L.cfmark.d, inner)
+                else:
+                    ora.ora_cf_jacobi(dptr(xr), C.byref(L.A), dptr(b), sweeps, L.cfmark.d)
+                assert np.array_equal(xg.view(np.uint64), xr.view(np.uint64)), (inner, post)
+        finally:
+            D.close()
+
+
 @pytest.mark.parametrize("hname", ["bus_h", "p32_h", "a27_h"])
 @pytest.mark.parametrize("inner,inner_from", [(0, 2), (1, 1), (1, 2), (2, 2)])
 def test_solve_hybrid_krylov_bitwise(request, hname, inner, inner_from, row_path):
