@@ -10,3 +10,4 @@ from ._native import (  # noqa: F401
     hbm_used_bytes,
     generate, lib, part_save, read_mtx,
 )
+from .workloads import convdiff_csr  # noqa: F401

@@ -110,6 +110,7 @@ ABI_SYMBOLS = [
     "sss_hip_opts_default", "sss_hip_device_count", "sss_hip_mem_info", "sss_hip_hier_create", "sss_hip_hier_destroy",
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
+    "sss_hip_fgmres", "sss_hip_host_orth",
     "SSS_amg_save", "SSS_amg_load",
     "sss_hip_coarse_solve", "sss_hip_smooth", "sss_hip_sync", "sss_hip_level_info_get", "sss_hip_num_levels", "sss_hip_tail_from",
     "sss_hip_cycle_launches", "sss_hip_cycle_bytes",
@@ -189,6 +190,8 @@ def _declare(lib):
         "sss_hip_cycle": (C.c_int, [C.c_void_p]),
         "sss_hip_residual_norm": (C.c_int, [C.c_void_p, _dbl_p]),
         "sss_hip_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int, P(C.c_int), _dbl_p, _dbl_p, C.c_int]),
+        "sss_hip_fgmres": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, P(C.c_int), _dbl_p, _dbl_p, C.c_int]),
+        "sss_hip_host_orth": (C.c_int, [C.c_int, C.c_int, _dbl_p, _dbl_p, _dbl_p, _dbl_p]),
         "SSS_amg_save": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "SSS_amg_load": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "sss_hip_coarse_solve": (C.c_int, [C.c_void_p]),
@@ -426,6 +429,16 @@ class DeviceHierarchy:
         hist = np.zeros(max(maxit, 1))
         its, rel = C.c_int(), C.c_double()
         self._check(lib().sss_hip_pcg(self.h, tol, maxit, C.byref(its), C.byref(rel), dptr(hist), len(hist)), "pcg")
+        return its.value, hist[: its.value].copy()
+
+    def fgmres(self, tol: float, restart: int = 20, maxit: int = 100):
+        """AMG-preconditioned flexible GMRES(restart) on level 0 (b, x uploaded as for cycle()), for
+        operators that are not symmetric positive definite; returns (iterations, history of the
+        relative residual estimate)."""
+        hist = np.zeros(max(maxit, 1))
+        its, rel = C.c_int(), C.c_double()
+        self._check(lib().sss_hip_fgmres(self.h, tol, restart, maxit, C.byref(its), C.byref(rel), dptr(hist), len(hist)),
+                    "fgmres")
         return its.value, hist[: its.value].copy()
 
     def smooth(self, level: int, post: bool):

@@ -595,6 +595,24 @@ int launch_axpy_ratio(int n, const double *num, const double *den, double sign, 
 int launch_xpby_ratio(int n, const double *num, const double *numold, const double *den, const double *z, double *p,
                       hipStream_t s);
 
+// ---- multi-vector orthogonalisation for the flexible GMRES (sss_fgmres.hip) ------------------
+// V: k columns back to back with leading dimension ld >= n (ld even, V and w 16-byte aligned).
+constexpr int kOrthBlocks = 1024;   // partial sums per dot product (fixed grid, fixed order)
+// doubles of `part` for a step against up to k columns: the norm's partials, then k dots' partials
+inline size_t orth_part_doubles(int k) { return (size_t)kOrthBlocks * (k + 1) + kFinalScratch; }
+// part[i * kOrthBlocks + b] = workgroup b's share of <w, v_i>, i < k
+int launch_multi_dot(int n, int k, const double *V, size_t ld, const double *w, double *part, hipStream_t s);
+// c[i] = sum of part[i][.]; hcol (optional): hcol[i] = c[i] (first) or hcol[i] + c[i]
+int launch_multi_final(int k, const double *part, double *c, double *hcol, bool first, hipStream_t s);
+// w += sign * sum_i coef[i] v_i (coef on the device); npart (optional): kOrthBlocks partials of ||w||^2
+int launch_multi_axpy(int n, int k, const double *V, size_t ld, const double *coef, double sign, double *w,
+                      double *npart, hipStream_t s);
+// w /= *nrm (*nrm on the device; zero leaves w unchanged)
+int launch_scale_inv(int n, double *w, const double *nrm, hipStream_t s);
+// CGS2 of w against V: hcol[0 .. k) = c1 + c2, hcol[k] = ||w||; c: k doubles, part: orth_part_doubles(k)
+int launch_orth_step(int n, int k, const double *V, size_t ld, double *w, double *part, double *c, double *hcol,
+                     hipStream_t s);
+
 // ---- coarse solvers ------------------------------------------------------------------------
 struct CoarseDirect {
     int n = 0;

@@ -78,10 +78,50 @@ static void check(int rc, const char *where)
     if (rc != 0) sss_fatal(where, "GPU engine call failed");
 }
 
+/* SSS_HIP_OUTER=fgmres[:<restart>]: the restart length of the flexible GMRES that replaces the
+ * V-cycle loop (20 when not given); 0 = unset or anything else, the reference's loop. */
+static int outer_fgmres_restart(void)
+{
+    const char *e = getenv("SSS_HIP_OUTER");
+    if (!e || strncmp(e, "fgmres", 6) != 0) return 0;
+    if (e[6] == '\0') return 20;
+    if (e[6] != ':') return 0;
+    if (atoi(e + 7) < 1) sss_fatal(__func__, "SSS_HIP_OUTER=fgmres:<restart> needs restart >= 1");
+    return atoi(e + 7);
+}
+
+/* the outer iteration as AMG-preconditioned FGMRES: the same rows of output, from its history */
+static SSS_RTN solve_fgmres(SSS_AMG *mg, sss_hip_hier *h, int restart, double sumb)
+{
+    const int max_it = mg->pars.max_it;
+    SSS_RTN rtn = {0.0, 0.0, 0};
+    double *hist = (double *)calloc((size_t)(max_it > 0 ? max_it : 1), sizeof(double));
+    double absres0 = sumb, absres = 0.0, relres = 0.0;
+    int iters = 0;
+    if (!hist) sss_fatal(__func__, "out of memory");
+    sss_trace_push("SSS_amg_solve fgmres");
+    check(sss_hip_fgmres(h, mg->pars.tol, restart, max_it, &iters, &relres, hist, max_it), __func__);
+    sss_trace_pop();
+    for (int iter = 1; iter <= iters; ++iter) {
+        absres = hist[iter - 1] * sumb;
+        SSS_print_itinfo(STOP_REL_RES, iter, hist[iter - 1], absres, absres / absres0);
+        absres0 = absres;
+    }
+    free(hist);
+    /* rtn from the true residual of the returned x; this also leaves r in the level-0 wp */
+    check(sss_hip_residual_norm(h, &absres), __func__);
+    rtn.ares = absres;
+    rtn.rres = absres / sumb;
+    rtn.nits = iters;
+    mg->rtn = rtn;
+    return rtn;
+}
+
 /* ---- outer loop -------------------------------------------------------------------- */
 SSS_RTN SSS_amg_solve(SSS_AMG *mg, SSS_VEC *x, SSS_VEC *b)
 {
     const int max_it = mg->pars.max_it;
+    const int fgmres = outer_fgmres_restart();
     const double tol = mg->pars.tol;
     const double sumb = SSS_blas_vec_norm2(b);
     double absres0 = sumb, t0;
@@ -111,7 +151,8 @@ SSS_RTN SSS_amg_solve(SSS_AMG *mg, SSS_VEC *x, SSS_VEC *b)
         return rtn;
     }
 
-    for (int iter = 1; iter <= max_it; ++iter) {
+    if (fgmres) rtn = solve_fgmres(mg, h, fgmres, sumb);
+    for (int iter = 1; !fgmres && iter <= max_it; ++iter) {
         double absres, relres, factor;
         sss_trace_push("SSS_amg_solve iteration %d", iter);
         sss_trace_push("V-cycle");

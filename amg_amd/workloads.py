@@ -12,6 +12,9 @@ an M-matrix, the class classical RS coarsening, Setup/SSS_coarsen.c, is built fo
   several thousand -- within +-50,000 labels (rows longer than the LDS tile: the load-balance path);
 
 conductances are log-normal.  Deterministic in (n, seed).  Rows are column-sorted CSR.
+
+convdiff(n, peclet): 7-point upwind convection-diffusion on an n^3 grid, the nonsymmetric M-matrix
+the flexible GMRES (sss_hip_fgmres) is tested and measured on.
 """
 from __future__ import annotations
 
@@ -66,6 +69,34 @@ def circuit(n: int = G3_CIRCUIT_ROWS, seed: int = 7, shift: float = 1e-2):
     A.sum_duplicates()
     A.sort_indices()
     return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+
+
+def convdiff(n: int, peclet: float = 2.0):
+    """(row_ptr, col_idx, val) of 7-point first-order upwind convection-diffusion on an n^3 grid:
+    -lap(u) + c . grad(u), c along (+x, +y, +z), cell Peclet number `peclet` per axis, h = 1.
+    Unknown (i, j, k) -> row i + n*(j + n*k), columns ascending, Dirichlet boundaries (off-grid
+    neighbours dropped).  Diagonal 6 + 3p, the upwind neighbours (-x, -y, -z) -(1 + p), the others
+    -1: a nonsymmetric M-matrix, interior rows summing to zero.  peclet = 0 is generate(7, n)."""
+    p = float(peclet)
+    N = n ** 3
+    r = np.arange(N, dtype=np.int32)
+    i, j, k = r % n, (r // n) % n, r // (n * n)
+    mask = np.ones((N, 7), dtype=bool)   # stencil order of ascending columns: -z -y -x 0 +x +y +z
+    mask[:, 0], mask[:, 1], mask[:, 2] = k > 0, j > 0, i > 0
+    mask[:, 4], mask[:, 5], mask[:, 6] = i < n - 1, j < n - 1, k < n - 1
+    stride = np.array([-n * n, -n, -1, 0, 1, n, n * n], dtype=np.int32)
+    vals = np.array([-(1.0 + p)] * 3 + [6.0 + 3.0 * p] + [-1.0] * 3)
+    rp = np.zeros(N + 1, dtype=np.int32)
+    np.cumsum(mask.sum(axis=1), out=rp[1:])
+    ci = (r[:, None] + stride[None, :])[mask]
+    v = np.broadcast_to(vals, (N, 7))[mask]
+    return rp, ci, v
+
+
+def convdiff_csr(n: int, peclet: float = 2.0):
+    """convdiff(n, peclet) as an amg_amd.NumpyCSR (its .mat is an SSS_MAT view)."""
+    from ._native import NumpyCSR
+    return NumpyCSR(*convdiff(n, peclet))
 
 
 def circuit_csr(n: int = G3_CIRCUIT_ROWS, seed: int = 7):

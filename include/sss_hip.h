@@ -133,6 +133,21 @@ int SSS_amg_load(SSS_AMG *mg, const char *path);
  * preconditioner.  Stops when ||r_k||/||b|| < tol or after maxit iterations; hist (optional)
  * receives the relative residual of each iteration. */
 int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, double *relres, double *hist, int hist_cap);
+/* AMG-preconditioned flexible GMRES(restart) on level 0, for operators that are not symmetric
+ * positive definite (an engine extension, like sss_hip_pcg): right preconditioning with one V-cycle
+ * on (v_j, 0) per iteration, Arnoldi by classical Gram-Schmidt applied twice in fused multi-vector
+ * kernels (deterministic, no atomics), Givens rotations on the host; one read-back of j + 2 doubles
+ * per iteration.  Right-hand side = the level-0 b vector (restored on return), initial guess /
+ * result = the level-0 x vector.  Stops when the estimate |g_{j+1}| / ||b|| < tol or after maxit
+ * iterations in total (restart > maxit is clamped); hist (optional) receives the estimate of each
+ * iteration.  ||b|| = 0: x = 0, no iteration.  restart < 1: ERROR_INPUT_PAR; a non-finite norm:
+ * ERROR_SOLVER_EXIT.
+ * Workspace, allocated at the first call, regrown when restart grows and freed with the hierarchy:
+ * (2 restart + 3) vectors of n0 doubles (n0 rounded up to even) -- the bases V (restart + 1) and Z
+ * (restart), and the saved b and x -- plus 1024 (restart + 1) + 256 doubles of partial sums.  For
+ * the 7-point 400^3 problem with restart 20 that is 43 x 0.512 GB = 22 GB. */
+int sss_hip_fgmres(sss_hip_hier *h, double tol, int restart, int maxit, int *iters, double *relres, double *hist,
+                   int hist_cap);
 /* The coarsest-level solve alone (on the level vectors of the coarsest level). */
 int sss_hip_coarse_solve(sss_hip_hier *h);
 /* Pre (post = 0) or post (post = 1) smoothing of one level. */
@@ -189,6 +204,10 @@ int sss_hip_spmv(const sss_hip_spmv_plan *p, int op, double alpha, const int *d_
 int sss_hip_host_spmv(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
                       double *y, int cap);
 int sss_hip_host_smooth(const SSS_SMTR *s, int post);
+/* One orthogonalisation step of sss_hip_fgmres on host data, through the same kernels: V holds k
+ * columns of n doubles back to back; w is orthogonalised against them in place (not normalised),
+ * hcol[0 .. k) receives the Hessenberg coefficients and *norm the 2-norm of the new w. */
+int sss_hip_host_orth(int n, int k, const double *V, double *w, double *hcol, double *norm);
 /* The three host-memory entry points keep the device form of their operator (keyed by a content
  * hash of the CSR arrays, the use and the device) in a small cache, so a caller that loops over
  * them with the same matrix uploads it once; this releases the cached device objects. */
