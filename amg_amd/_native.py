@@ -91,6 +91,8 @@ class SSS_HIP_LEVEL_INFO(C.Structure):
 
 
 SMOOTH = {"exact": 0, "hybrid": 1, "jacobi": 2}
+#: SSS_COARSEN_TYPE values of SSS_AMG_PARS.cs_type (3 is an engine extension, the parallel split)
+COARSE_RS, COARSE_PMIS = 1, 3
 COARSE = {"krylov": 0, "direct": 1}
 VEC = {"b": 0, "x": 1, "wp": 2}
 SPMV = {"mxy": 0, "amxpy": 1, "resid": 2, "acc": 3}
@@ -108,7 +110,7 @@ ABI_SYMBOLS = [
     "SSS_amg_setup", "SSS_amg_coarsen", "SSS_amg_interp", "SSS_amg_interp_trunc", "interp_DIR", "SSS_mat_read",
     "SSS_amg_pars_init", "SSS_amg_pars_print", "mmio_info", "mmio_data",
     "sss_hip_opts_default", "sss_hip_device_count", "sss_hip_mem_info", "sss_hip_hier_create", "sss_hip_hier_destroy",
-    "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap",
+    "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth",
     "SSS_amg_save", "SSS_amg_load",
@@ -185,6 +187,8 @@ def _declare(lib):
                                               P(C.c_double)]),
         "sss_hip_hier_destroy": (None, [C.c_void_p]),
         "sss_hip_rap": (C.c_int, [P(SSS_MAT), P(SSS_MAT), P(SSS_MAT), P(SSS_MAT)]),
+        "sss_hip_pmis": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
+        "sss_pmis_host": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
         "sss_hip_upload_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_download_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_cycle": (C.c_int, [C.c_void_p]),
@@ -296,6 +300,25 @@ def default_pars() -> SSS_AMG_PARS:
     return p
 
 
+def pmis(rp, ci, device: bool = False):
+    """PMIS C/F split (cs_type COARSE_PMIS) of a compacted strength matrix given as CSR row pointers
+    and columns: (marks, C points, rounds), on the host (sss_pmis_host) or on the GPU (sss_hip_pmis).
+    Raises RuntimeError with the error code when the split fails; marks are then untouched (-7)."""
+    rp = np.ascontiguousarray(rp, dtype=np.int32)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    n = len(rp) - 1
+    S = SSS_IMAT(n, n, len(ci), iptr(rp), iptr(ci) if len(ci) else None, None)
+    mark = np.full(max(n, 1), -7, np.int32)
+    nc, rounds = C.c_int(-1), C.c_int(-1)
+    fn = lib().sss_hip_pmis if device else lib().sss_pmis_host
+    rc = fn(C.byref(S), iptr(mark), C.byref(nc), C.byref(rounds))
+    if rc != 0:
+        err = RuntimeError(f"PMIS split failed ({rc})")
+        err.rc, err.mark = rc, mark[:n]
+        raise err
+    return mark[:n], nc.value, rounds.value
+
+
 def generate(kind: int, n: int, nz: int | None = None, z0: int = 0, z1: int | None = None) -> SSS_MAT:
     """7-point or 27-point (anisotropic) stencil on an n*n*nz grid, rows of planes [z0, z1)."""
     nz = n if nz is None else nz
@@ -362,10 +385,11 @@ class DeviceHierarchy:
                  device: int = -1, verbose: int = 0, relabel: int | None = None, graph: int | None = None,
                  inner: int | None = None, inner_from: int | None = None, sorted_tiles: int | None = None,
                  sum_order: int | None = None, setup_from: SSS_MAT | None = None, inner_long: int | None = None,
-                 formats: str | None = None):
+                 formats: str | None = None, pars: SSS_AMG_PARS | None = None):
         """setup_from: build the Hierarchy from this operator here, with the levels uploaded while
         the setup is still running (sss_hip_setup_create); H must then be None and self.H is the
-        new Hierarchy.  self.times = (setup s, mirror s after the setup, of which waiting)."""
+        new Hierarchy (set up with pars, default: default_pars()).  self.times = (setup s, mirror s
+        after the setup, of which waiting)."""
         o = SSS_HIP_OPTS()
         lib().sss_hip_opts_default(C.byref(o))
         o.smoother, o.coarse, o.row_cap, o.device, o.verbose = SMOOTH[smoother], COARSE[coarse], row_cap, device, verbose
@@ -388,7 +412,7 @@ class DeviceHierarchy:
         if setup_from is not None:
             if H is not None:
                 raise ValueError("setup_from builds its own Hierarchy: pass H=None")
-            H = Hierarchy(None)
+            H = Hierarchy(None, pars)
             t = (C.c_double * 3)()
             self.H = H
             self.h = lib().sss_hip_setup_create(C.byref(H.mg), C.byref(setup_from), C.byref(H.pars), C.byref(o), t)

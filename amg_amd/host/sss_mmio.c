@@ -338,6 +338,13 @@ void SSS_amg_pars_init(SSS_AMG_PARS *pars)
     pars->max_row_sum = 0.9;
     pars->strong_threshold = 0.3;
     pars->trunc_threshold = 0.2;
+    /* engine extension for drop-in callers, who cannot change their pars code:
+     * SSS_SETUP_COARSEN=pmis selects the parallel split and its interpolation partner */
+    const char *cs = getenv("SSS_SETUP_COARSEN");
+    if (cs && strcmp(cs, "pmis") == 0) {
+        pars->cs_type = SSS_COARSE_PMIS;
+        pars->interp_type = intERP_STD;
+    }
 }
 
 /* SSS_main.c:67-119 — byte-identical stdout. */

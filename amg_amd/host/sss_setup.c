@@ -15,6 +15,11 @@
  *   Galerkin RAP ................ SSS_matvec.c:398-534
  *   level loop .................. Setup/SSS_SETUP.cu:36-178
  *
+ * One engine extension, off unless asked for: cs_type SSS_COARSE_PMIS (3) replaces the serial RS
+ * first pass by the parallel PMIS split (pmis_split below; on the device sss_hip_pmis,
+ * amg_amd/csrc/sss_pmis.hip).  No F-F cleanup runs after it; interp_type 2 is its partner.  With
+ * cs_type 1 nothing here differs from the reference.
+ *
  * The measure lists are kept as an array of FIFO buckets indexed by measure instead of the
  * reference's heap-allocated sorted list of list nodes with element-level linked lists
  * (lists/where); every insert/remove happens in the same order, so the head of the maximal
@@ -454,6 +459,123 @@ static int rs_split(const SSS_MAT *A, SSS_IMAT *S, SSS_IVEC *vertices)
     return ncoarse;
 }
 
+/* ======================================================================================
+ * PMIS C/F split (cs_type SSS_COARSE_PMIS; an engine extension, DESIGN.md "PMIS coarsening").
+ * Input: the compacted S.  lambda_i = stored entries of S with column i; key_i = lambda_i << 32 |
+ * h(i) with h a bijection of uint32, so keys are pairwise distinct and there is no tie rule.
+ * Start: empty S row -> ISPT, else lambda_i = 0 -> FGPT, else undecided.  One round, on the marks
+ * as they stand at its start: (a) an undecided i whose key exceeds the key of every undecided j in
+ * S_i u S^T_i becomes CGPT; (b) then a still undecided i with a CGPT point in S_i becomes FGPT.
+ * Rounds repeat until nobody is undecided (the largest undecided key always becomes C).  The marks
+ * depend on S alone: this row-parallel host form and the device form (amg_amd/csrc/sss_pmis.hip)
+ * agree bit for bit, whatever the thread count.
+ * ====================================================================================== */
+static inline uint32_t pmis_hash(uint32_t i)
+{
+    i ^= i >> 16;
+    i *= 0x7feb352dU;
+    i ^= i >> 15;
+    i *= 0x846ca68bU;
+    i ^= i >> 16;
+    return i;
+}
+
+enum { kPmisMaxRounds = 4096 };
+
+/* Host PMIS split of a compacted S.  Returns the C-point count, or ERROR_UNKNOWN past the round cap. */
+static int pmis_split(SSS_IMAT *S, int *mark, int *rounds_out)
+{
+    const int n = S->num_rows;
+    const int *ia = S->row_ptr, *ja = S->col_idx;
+    SSS_IMAT ST;
+    if (ia[n] > 0) {
+        ST = SSS_imat_trans(S);
+    } else {   /* no entry at all (never from the setup: drop_weak has failed then) */
+        memset(&ST, 0, sizeof(ST));
+        ST.row_ptr = (int *)SSS_calloc((size_t)n + 1, sizeof(int));
+    }
+    const int *ta = ST.row_ptr, *tj = ST.col_idx;
+    uint64_t *key = (uint64_t *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(uint64_t));
+    int *next = (int *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(int));
+    long long undecided = 0;
+    int ncoarse = 0, rounds = 0;
+
+#pragma omp parallel for schedule(static) reduction(+ : undecided) if (n > 4096)
+    for (int i = 0; i < n; ++i) {
+        const int lambda = ta[i + 1] - ta[i];
+        key[i] = (uint64_t)(uint32_t)lambda << 32 | pmis_hash((uint32_t)i);
+        if (ia[i + 1] == ia[i]) mark[i] = ISPT;
+        else if (lambda == 0) mark[i] = FGPT;
+        else mark[i] = UNPT, undecided++;
+    }
+    while (undecided > 0 && rounds < kPmisMaxRounds) {
+        int newc = 0;
+        rounds++;
+        /* (a) local maxima of the key among the undecided become C (reads mark, writes next) */
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : newc) if (n > 4096)
+        for (int i = 0; i < n; ++i) {
+            int top = mark[i] == UNPT;
+            for (int q = ia[i]; top && q < ia[i + 1]; ++q)
+                top = !(mark[ja[q]] == UNPT && key[ja[q]] > key[i]);
+            for (int q = ta[i]; top && q < ta[i + 1]; ++q)
+                top = !(mark[tj[q]] == UNPT && key[tj[q]] > key[i]);
+            next[i] = top ? CGPT : mark[i];
+            newc += top;
+        }
+        ncoarse += newc;
+        /* (b) the undecided that depend on a C point become F (reads next, writes mark) */
+        undecided = 0;
+#pragma omp parallel for schedule(dynamic, 1024) reduction(+ : undecided) if (n > 4096)
+        for (int i = 0; i < n; ++i) {
+            int m = next[i];
+            if (m == UNPT) {
+                for (int q = ia[i]; q < ia[i + 1]; ++q)
+                    if (next[ja[q]] == CGPT) { m = FGPT; break; }
+                undecided += m == UNPT;
+            }
+            mark[i] = m;
+        }
+    }
+    free(key);
+    free(next);
+    SSS_imat_destroy(&ST);
+    if (rounds_out) *rounds_out = rounds;
+    return undecided > 0 ? ERROR_UNKNOWN : ncoarse;
+}
+
+/* The host split on a given compacted S (tests; what the device split is checked against). */
+int sss_pmis_host(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds)
+{
+    if (!S || !mark || S->num_rows <= 0) return ERROR_INPUT_PAR;
+    SSS_IMAT s = *S;
+    const int nc = pmis_split(&s, mark, rounds);
+    if (nc < 0) return nc;
+    if (ncoarse) *ncoarse = nc;
+    return 0;
+}
+
+/* drop_weak + the PMIS split: on the device when one is present, the level has at least
+ * SSS_SETUP_GPU_PMIS_MIN strong entries and SSS_SETUP_GPU_PMIS is not 0; else, or when the device
+ * split fails, on the host.  Returns the C-point count (or <0). */
+static int pmis_coarsen(SSS_IMAT *S, SSS_IVEC *vertices)
+{
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const char *gp = getenv("SSS_SETUP_GPU_PMIS"), *gpm = getenv("SSS_SETUP_GPU_PMIS_MIN");
+    const int gpu_min = (gpm && *gpm) ? atoi(gpm) : SSS_SETUP_GPU_PMIS_MIN_DEFAULT;
+    int ncoarse, rounds = 0, on_device = 0;
+    const double t0 = SSS_get_time();
+    ncoarse = drop_weak(S);
+    if (ncoarse < 0) return ncoarse;
+    const double t1 = SSS_get_time();
+    if (!(gp && gp[0] == '0') && S->num_nnzs >= gpu_min && sss_hip_device_count() > 0)
+        on_device = sss_hip_pmis(S, vertices->d, &ncoarse, &rounds) == 0;
+    if (!on_device) ncoarse = pmis_split(S, vertices->d, &rounds);
+    if (timing)
+        fprintf(stderr, "[setup]   PMIS split: drop %.3f s, %s split %.4f s, %d rounds, %d strong entries\n", t1 - t0,
+                on_device ? "device" : "host", SSS_get_time() - t1, rounds, S->num_nnzs);
+    return ncoarse;
+}
+
 /* Setup/SSS_coarsen.c:501-574.  Note: the tentative-C state (pending, pending_owner,
  * tentative) deliberately persists across rows exactly as in the reference. */
 static int cleanup_ff(const SSS_IMAT *S, SSS_IVEC *vertices, int n, int ncoarse)
@@ -634,23 +756,28 @@ int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS
     const double t0 = SSS_get_time();
     strong_couplings(A, S, pars);
     const double t1 = SSS_get_time();
+    const int pmis = pars->cs_type == SSS_COARSE_PMIS;
+    const char *split = pmis ? "PMIS" : "RS";
     if (pars->cs_type == SSS_COARSE_RS) ncoarse = rs_split(A, S, vertices);
+    else if (pmis) ncoarse = pmis_coarsen(S, vertices);
     else if (pars->cs_type != SSS_COARSE_RSP) SSS_exit_on_errcode(ERROR_AMG_COARSE_TYPE, __func__);
     if (ncoarse <= 0) return ERROR_UNKNOWN;
     const double t2 = SSS_get_time();
     if (pars->interp_type == intERP_DIR) {
-        ncoarse = cleanup_ff(S, vertices, A->num_rows, ncoarse);
+        /* the F-F cleanup never runs after PMIS: it promotes until every strong F-F pair shares a
+         * C point, which undoes the split (DESIGN.md "PMIS coarsening") */
+        if (!pmis) ncoarse = cleanup_ff(S, vertices, A->num_rows, ncoarse);
         const double t3 = SSS_get_time();
         direct_pattern(P, S, vertices, A->num_rows, ncoarse);
         if (timing)
-            fprintf(stderr, "[setup]   coarsen: strength %.3f s, RS split %.3f s, F-F cleanup %.3f s, P pattern %.3f s\n",
-                    t1 - t0, t2 - t1, t3 - t2, SSS_get_time() - t3);
+            fprintf(stderr, "[setup]   coarsen: strength %.3f s, %s split %.3f s, F-F cleanup %.3f s, P pattern %.3f s\n",
+                    t1 - t0, split, t2 - t1, t3 - t2, SSS_get_time() - t3);
     } else if (pars->interp_type == intERP_STD) {   /* no F-F cleanup before the standard pattern */
         const double t3 = SSS_get_time();
         std_pattern(P, S, vertices, A->num_rows, ncoarse);
         if (timing)
-            fprintf(stderr, "[setup]   coarsen: strength %.3f s, RS split %.3f s, standard P pattern %.3f s\n", t1 - t0,
-                    t2 - t1, SSS_get_time() - t3);
+            fprintf(stderr, "[setup]   coarsen: strength %.3f s, %s split %.3f s, standard P pattern %.3f s\n", t1 - t0,
+                    split, t2 - t1, SSS_get_time() - t3);
     } else {
         SSS_exit_on_errcode(ERROR_AMG_interp_type, __func__);
     }

@@ -119,7 +119,10 @@ typedef struct SSS_RTN_ {          /* SSS_main.h:154-160; sizeof 24 */
     int nits;
 } SSS_RTN;
 
-typedef enum SSS_COARSEN_TYPE_ { SSS_COARSE_RS = 1, SSS_COARSE_RSP = 2 } SSS_COARSEN_TYPE;
+/* 1 and 2 are the reference's; SSS_COARSE_PMIS is an engine extension: the parallel PMIS split
+ * (no serial pass; on the GPU for large levels), meant for interp_type intERP_STD.
+ * SSS_SETUP_COARSEN=pmis makes SSS_amg_pars_init choose it (cs_type 3, interp_type 2). */
+typedef enum SSS_COARSEN_TYPE_ { SSS_COARSE_RS = 1, SSS_COARSE_RSP = 2, SSS_COARSE_PMIS = 3 } SSS_COARSEN_TYPE;
 
 typedef struct SSS_AMG_PARS_ {     /* SSS_main.h:170-194; sizeof 104 */
     int cycle_type;

@@ -107,6 +107,22 @@ sss_hip_hier *sss_hip_setup_create(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, 
  * (default 48); SSS_SETUP_GPU_RAP=0 keeps every product on the host. */
 int sss_hip_rap(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P, SSS_MAT *C);
 
+/* The PMIS C/F split (cs_type SSS_COARSE_PMIS; the rule: DESIGN.md "PMIS coarsening") of a compacted
+ * strength matrix S (row_ptr, col_idx; square) on the GPU: S is uploaded, the rounds run as ordinary
+ * launches steered by the host, mark (n ints: CGPT / FGPT / ISPT) is downloaded.  *ncoarse = the
+ * C points, *rounds = the rounds it took (either may be NULL).  The marks depend on S alone and
+ * equal the host split's.  Returns 0, or an error code with mark untouched (no device, no rows, no
+ * memory, more than 4096 rounds); the setup then runs the host split.  The setup uses it, when a
+ * device is present, for levels with at least SSS_SETUP_GPU_PMIS_MIN entries in S (default
+ * SSS_SETUP_GPU_PMIS_MIN_DEFAULT = 10^7: measured at 7-pt 400^3, the device split with its copies
+ * costs about 6 ms + 0.6 ns per entry, the host split on 16 threads 1.3 ns per entry, DESIGN.md
+ * 6.4); SSS_SETUP_GPU_PMIS=0 keeps every split on the host. */
+#define SSS_SETUP_GPU_PMIS_MIN_DEFAULT 10000000
+int sss_hip_pmis(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds);
+/* The same split on the host (OpenMP, row-parallel): what the setup runs without a device or on
+ * small levels, and what the device split is tested against.  0 or an error code. */
+int sss_pmis_host(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds);
+
 /* Progress hook of the setup (amg_amd/host/sss_setup.c): hook(ctx, mg, done, 0) once levels
  * 0 .. done-1 are final and none of them is the coarsest; hook(ctx, mg, num_levels - 1, 1) at
  * the end. */
