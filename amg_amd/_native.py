@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "SSS_amg_pars_init", "SSS_amg_pars_print", "mmio_info", "mmio_data",
     "sss_hip_opts_default", "sss_hip_device_count", "sss_hip_mem_info", "sss_hip_hier_create", "sss_hip_hier_destroy",
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
+    "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth",
     "SSS_amg_save", "SSS_amg_load",
@@ -189,6 +190,10 @@ def _declare(lib):
         "sss_hip_rap": (C.c_int, [P(SSS_MAT), P(SSS_MAT), P(SSS_MAT), P(SSS_MAT)]),
         "sss_hip_pmis": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
         "sss_pmis_host": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
+        "sss_hip_std_pattern": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
+        "sss_std_pattern_host": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
+        "sss_hip_interp_std": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double]),
+        "SSS_mat_struct_create": (SSS_MAT, [C.c_int, C.c_int, C.c_int]),
         "sss_hip_upload_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_download_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_cycle": (C.c_int, [C.c_void_p]),
@@ -317,6 +322,66 @@ def pmis(rp, ci, device: bool = False):
         err.rc, err.mark = rc, mark[:n]
         raise err
     return mark[:n], nc.value, rounds.value
+
+
+def _imat(rp, ci):
+    rp = np.ascontiguousarray(rp, dtype=np.int32)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    n = len(rp) - 1
+    return SSS_IMAT(n, n, len(ci), iptr(rp), iptr(ci) if len(ci) else None, None), (rp, ci)
+
+
+def std_pattern(rp, ci, mark, device: bool = False):
+    """Pattern of the standard interpolation (interp_type 2) from a compacted strength matrix (CSR row
+    pointers and columns) and the C/F marks: (P row_ptr, P col_idx), columns in fine numbering and
+    discovery order, on the host (sss_std_pattern_host) or on the GPU (sss_hip_std_pattern).  Raises
+    RuntimeError with the error code (.rc) when it fails."""
+    S, keep = _imat(rp, ci)
+    mark = np.ascontiguousarray(mark, dtype=np.int32)
+    P = SSS_MAT()
+    fn = lib().sss_hip_std_pattern if device else lib().sss_std_pattern_host
+    rc = fn(C.byref(S), iptr(mark), int((mark == 1).sum()), C.byref(P))
+    if rc != 0:
+        err = RuntimeError(f"standard pattern failed ({rc})")
+        err.rc = rc
+        raise err
+    prp, pci, _ = csr_arrays(P)
+    lib().SSS_mat_destroy(C.byref(P))
+    return prp, pci
+
+
+def interp_std(A_csr, S_csr, mark, P_pattern, trunc: float, device: bool = False):
+    """Standard interpolation on a pattern: the weights, the coarse renumbering of the columns and the
+    truncation at `trunc`.  A_csr = (row_ptr, col_idx, val), S_csr = (row_ptr, col_idx), P_pattern =
+    (row_ptr, col_idx) as std_pattern returns it.  Returns (row_ptr, col_idx, val, ncols), from the host
+    (SSS_amg_interp) or from the GPU (sss_hip_interp_std).  Raises RuntimeError with the error code
+    (.rc) when the device call fails."""
+    Am = NumpyCSR(*A_csr)
+    S, keep = _imat(*S_csr)
+    mark = np.ascontiguousarray(mark, dtype=np.int32)
+    prp = np.ascontiguousarray(P_pattern[0], dtype=np.int32)
+    pci = np.ascontiguousarray(P_pattern[1], dtype=np.int32)
+    n = len(prp) - 1
+    # the truncation frees P's arrays: they must be the library's, not numpy's
+    P = lib().SSS_mat_struct_create(n, int((mark == 1).sum()), len(pci))
+    C.memmove(P.row_ptr, prp.ctypes.data, prp.nbytes)
+    if len(pci):
+        C.memmove(P.col_idx, pci.ctypes.data, pci.nbytes)
+    try:
+        if device:
+            rc = lib().sss_hip_interp_std(C.byref(Am.mat), C.byref(S), iptr(mark), C.byref(P), trunc)
+            if rc != 0:
+                err = RuntimeError(f"standard interpolation failed ({rc})")
+                err.rc = rc
+                raise err
+        else:
+            pars = default_pars()
+            pars.interp_type, pars.trunc_threshold = 2, trunc
+            verts = SSS_IVEC(len(mark), iptr(mark))
+            lib().SSS_amg_interp(C.byref(Am.mat), C.byref(verts), C.byref(P), C.byref(S), C.byref(pars))
+        return (*csr_arrays(P), P.num_cols)
+    finally:
+        lib().SSS_mat_destroy(C.byref(P))
 
 
 def generate(kind: int, n: int, nz: int | None = None, z0: int = 0, z1: int | None = None) -> SSS_MAT:

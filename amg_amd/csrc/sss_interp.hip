@@ -1,0 +1,786 @@
+// sss_interp.hip — the standard interpolation of the setup (interp_type intERP_STD) on the GPU: the
+// P pattern (amg_amd/host/sss_setup.c std_pattern) and the weights with the coarse renumbering and the
+// truncation (interp_STD, interp_trunc_par), bit for bit the host result.
+//
+// Both are row-independent; G lanes of one wavefront share a row, G chosen from the average row of S.
+// What makes the host result depend on order is kept per row:
+//
+//   pattern  the candidates of an F row i are the C points of S_i and, for every F point k != i of
+//            S_i, the C points of S_k, numbered in the host's discovery order.  Each candidate claims
+//            its column's slot of a per-row hash table with an atomicMin of its number; a second walk
+//            keeps the candidates that own their slot, at offsets from an in-order ballot of the group.
+//   weights  hat a lives in a per-row hash table keyed by column.  A slot has one owner lane
+//            (slot mod G), and only the owner adds to it: the contributions of a chunk of G entries
+//            are handed to the owners lane by lane, in stored order, so every slot sees its terms in
+//            the host's (j, m) order.  The scalars of the row (hat a_ii, alN, alP) are computed by
+//            every lane of the group from the same loads in the same order.
+//
+// The table of a row is in LDS when the row's candidate bound (its S row plus the S rows of its strong
+// F neighbours) fits the group's share of it, else in a global array sized from the bound inside the
+// same call.  Probe loops are bounded by the capacity, every index read from A, S and P is
+// range-checked, and what cannot happen on consistent input (a strong column absent from the A row,
+// a C column absent from the pattern row, a full table) raises a flag the host reads back: the call
+// then fails with P untouched.  Ordinary launches only; nothing waits on another workgroup.
+#include "sss_engine.hpp"
+
+#include <hipcub/hipcub.hpp>
+
+#include <climits>
+#include <cstring>
+
+namespace sss {
+
+namespace {
+
+constexpr int kLdsSlots = 2048;          // table slots per workgroup (8 G per group of G lanes)
+constexpr int kMaxBound = 1 << 27;       // candidate bound of one row (its table has twice as many slots)
+enum : int { kErrIndex = 1, kErrStrongCol = 2, kErrPatternCol = 4, kErrTableFull = 8, kErrBound = 16 };
+
+struct Csr {
+    int n, nnz;
+    const int *rp, *ci;
+    const double *v;
+};
+
+__host__ __device__ __forceinline__ int tab_cap(int need)
+{
+    int c = 2;
+    while (c < 2 * need) c <<= 1;
+    return c;
+}
+
+__device__ __forceinline__ unsigned tab_hash(int col, int cap) { return ((unsigned)col * 2654435761u >> 7) & (unsigned)(cap - 1); }
+
+__device__ __forceinline__ void span(const Csr &M, int i, int &lo, int &hi)
+{
+    lo = max(M.rp[i], 0);
+    hi = max(min(M.rp[i + 1], M.nnz), lo);
+}
+
+// slot of col (inserted when absent), -1 when the table is full
+__device__ __forceinline__ int tab_insert(int *key, int cap, int col)
+{
+    unsigned s = tab_hash(col, cap);
+    for (int p = 0; p < cap; ++p, s = (s + 1) & (unsigned)(cap - 1)) {
+        const int prev = atomicCAS(&key[s], -1, col);
+        if (prev == -1 || prev == col) return (int)s;
+    }
+    return -1;
+}
+
+// slot of col, -1 when absent
+__device__ __forceinline__ int tab_find(const int *key, int cap, int col)
+{
+    unsigned s = tab_hash(col, cap);
+    for (int p = 0; p < cap; ++p, s = (s + 1) & (unsigned)(cap - 1)) {
+        const int k = key[s];
+        if (k == col) return (int)s;
+        if (k == -1) return -1;
+    }
+    return -1;
+}
+
+// Candidate bound of every F row (at least plen, the row's pattern length, when prp is given), the
+// capacity of its global table (0: the row's table is in LDS) and the rows that have one.
+__global__ __launch_bounds__(kBlock) void interp_bound(Csr S, const int *__restrict__ mark, const int *__restrict__ prp,
+                                                       int pnnz, int slots, int *__restrict__ need,
+                                                       long long *__restrict__ gcap, int *__restrict__ ctr)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= S.n) return;
+    long long b = 0;
+    if (mark[i] == FGPT) {
+        int lo, hi;
+        span(S, i, lo, hi);
+        b = hi - lo;
+        for (int q = lo; q < hi; ++q) {
+            const int k = S.ci[q];
+            if ((unsigned)k >= (unsigned)S.n) {
+                atomicOr(&ctr[0], kErrIndex);
+                continue;
+            }
+            if (mark[k] == FGPT && k != i) {
+                int klo, khi;
+                span(S, k, klo, khi);
+                b += khi - klo;
+            }
+        }
+        if (prp) b = max(b, (long long)(min(prp[i + 1], pnnz) - max(prp[i], 0)));
+    }
+    if (b > kMaxBound) {
+        atomicOr(&ctr[0], kErrBound);
+        b = 0;
+    }
+    need[i] = (int)b;
+    const bool glob = b > slots;
+    gcap[i] = glob ? tab_cap((int)b) : 0;
+    if (glob) atomicAdd(&ctr[1], 1);
+}
+
+// the table of row i: in the group's share of LDS, or at goff[i] of the global arrays
+__device__ __forceinline__ int row_table(int i, int grp, int slots, const int *need, const long long *goff, int *lkey,
+                                         int *gkey, int *&key, long long &off)
+{
+    const int b = need[i];
+    if (b > slots) {
+        off = goff[i];
+        key = gkey + off;
+        return tab_cap(b);
+    }
+    off = -1 - (long long)grp * slots;
+    key = lkey + grp * slots;
+    return min(slots, tab_cap(b));
+}
+
+template <int G>
+__device__ __forceinline__ unsigned long long group_ballot(bool p, int gl)
+{
+    const unsigned long long b = __ballot(p);
+    if (G == 64) return b;
+    const int gbase = (int)(threadIdx.x & 63) - gl;
+    return (b >> gbase) & ((1ull << (G & 63)) - 1ull);
+}
+
+// One walk over the candidates of F row i in discovery order.  CLAIM: every candidate claims its slot
+// with its sequence number.  Else: the candidates that own their slot are counted, and with FILL
+// written to out[] in order.  Returns the count (the same on every lane of the group).
+template <int G, bool CLAIM, bool FILL>
+__device__ __forceinline__ int pattern_walk(const Csr &S, const int *__restrict__ mark, int i, int gl, int *key, int *seq,
+                                            int cap, int *out, int room, int *err)
+{
+    int lo, hi, base = 0, kept = 0;
+    span(S, i, lo, hi);
+    for (int q = lo; q < hi; ++q) {
+        const int k = S.ci[q];
+        if ((unsigned)k >= (unsigned)S.n) continue;   // flagged by interp_bound
+        const int mk = mark[k];
+        int klo = q, khi = q + 1;                     // a C point: the one candidate k itself
+        if (mk == FGPT && k != i) span(S, k, klo, khi);
+        else if (mk != CGPT) continue;
+        for (int r0 = klo; r0 < khi; r0 += G) {
+            const int r = r0 + gl;
+            int h = -1;
+            if (r < khi) {
+                h = S.ci[r];
+                if ((unsigned)h >= (unsigned)S.n) {
+                    atomicOr(err, kErrIndex);
+                    h = -1;
+                } else if (mark[h] != CGPT) {
+                    h = -1;
+                }
+            }
+            const int s = base + (r - klo);
+            if (CLAIM) {
+                if (h >= 0) {
+                    const int slot = tab_insert(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else atomicMin(&seq[slot], s);
+                }
+            } else {
+                bool own = false;
+                if (h >= 0) {
+                    const int slot = tab_find(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else own = seq[slot] == s;
+                }
+                const unsigned long long m = group_ballot<G>(own, gl);
+                if (FILL && own) {
+                    const int o = kept + __popcll(m & ((1ull << gl) - 1ull));
+                    if (o < room) out[o] = h;
+                }
+                kept += __popcll(m);
+            }
+        }
+        base += khi - klo;
+    }
+    return kept;
+}
+
+// count (FILL false: cnt[i]) or fill (pci at prp[i]) of the pattern; G lanes per row
+template <int G, bool FILL>
+__global__ __launch_bounds__(kBlock) void pattern_rows(Csr S, const int *__restrict__ mark, int slots,
+                                                       const int *__restrict__ need, const long long *__restrict__ goff,
+                                                       int *__restrict__ gkey, int *__restrict__ gseq, int *__restrict__ cnt,
+                                                       const int *__restrict__ prp, int pnnz, int *__restrict__ pci,
+                                                       int *__restrict__ err)
+{
+    __shared__ int lkey[kLdsSlots], lseq[kLdsSlots];
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    const int i = row < S.n ? (int)row : -1;
+    const int mi = i >= 0 ? mark[i] : UNPT;
+    int *key = nullptr, *seq = nullptr, cap = 0;
+    if (mi == FGPT) {
+        long long off;
+        cap = row_table(i, grp, slots, need, goff, lkey, gkey, key, off);
+        seq = off >= 0 ? gseq + off : lseq + (-1 - off);
+        for (int s = gl; s < cap; s += G) {
+            key[s] = -1;
+            seq[s] = INT_MAX;
+        }
+    }
+    __syncthreads();
+    if (mi == FGPT) pattern_walk<G, true, false>(S, mark, i, gl, key, seq, cap, nullptr, 0, err);
+    __syncthreads();
+    if (mi == FGPT) {
+        int o = 0, room = 0;
+        if (FILL) {
+            o = max(prp[i], 0);
+            room = min(prp[i + 1], pnnz) - o;
+        }
+        // the fill writes what the count counted: the same walk over the same table
+        const int kept = pattern_walk<G, false, FILL>(S, mark, i, gl, key, seq, cap, pci + o, room, err);
+        if (FILL) {
+            if (kept != room && gl == 0) atomicOr(err, kErrPatternCol);
+        } else if (gl == 0) {
+            cnt[i] = kept;
+        }
+    } else if (i >= 0 && gl == 0) {
+        if (!FILL) cnt[i] = mi == CGPT ? 1 : 0;
+        else if (mi == CGPT) {
+            const int o = prp[i];
+            if ((unsigned)o < (unsigned)pnnz) pci[o] = i;
+        }
+    }
+}
+
+// step 0 of interp_STD for the F rows: the row's last diagonal entry, and in stored order the sums of
+// the strong-C entries, of the off-diagonal entries and of those whose column is not isolated
+__global__ __launch_bounds__(kBlock) void weights_sums(Csr A, Csr S, const int *__restrict__ mark, double *__restrict__ diag,
+                                                       double *__restrict__ csum, double *__restrict__ nsum,
+                                                       double *__restrict__ psum, int *__restrict__ err)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n || mark[i] != FGPT) return;
+    int lo, hi, slo, shi;
+    span(A, i, lo, hi);
+    span(S, i, slo, shi);
+    double cs = 0.0, ns = 0.0, ps = 0.0, d = 0.0;
+    for (int j = lo; j < hi; ++j) {
+        const int k = A.ci[j];
+        if ((unsigned)k >= (unsigned)A.n) {
+            atomicOr(err, kErrIndex);
+            continue;
+        }
+        const int mk = mark[k];
+        bool strong_c = false;
+        if (mk == CGPT)
+            for (int q = slo; q < shi && !strong_c; ++q) strong_c = S.ci[q] == k;
+        const double a = A.v[j];
+        if (strong_c) cs += a;
+        if (k == i) {
+            d = a;
+        } else {
+            ns += a;
+            if (mk != ISPT) ps += a;
+        }
+    }
+    diag[i] = d, csum[i] = cs, nsum[i] = ns, psum[i] = ps;
+}
+
+// position of the last entry of A's row [lo, hi) with column col, searched by the G lanes; -1 if none
+template <int G>
+__device__ __forceinline__ int group_find_last(const Csr &A, int lo, int hi, int col, int gl)
+{
+    int best = -1;
+    for (int m = lo + gl; m < hi; m += G)
+        if (A.ci[m] == col) best = m;
+    for (int o = G / 2; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, G));
+    return best;
+}
+
+// step 1 of interp_STD: the weights of the F rows on the pattern (fine column numbers), 1 for the C rows
+template <int G>
+__global__ __launch_bounds__(kBlock) void weights_rows(Csr A, Csr S, const int *__restrict__ mark, int slots,
+                                                       const int *__restrict__ need, const long long *__restrict__ goff,
+                                                       int *__restrict__ gkey, double *__restrict__ gacc,
+                                                       const int *__restrict__ prp, int pnnz, const int *__restrict__ pci,
+                                                       double *__restrict__ pv, const double *__restrict__ diag,
+                                                       const double *__restrict__ csum, const double *__restrict__ nsum,
+                                                       const double *__restrict__ psum, int *__restrict__ err)
+{
+    __shared__ int lkey[kLdsSlots];
+    __shared__ double lacc[kLdsSlots];
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    const int i = row < A.n ? (int)row : -1;
+    const int mi = i >= 0 ? mark[i] : UNPT;
+    int *key = nullptr, cap = 0, plo = 0, phi = 0;
+    double *acc = nullptr;
+    if (mi == FGPT) {
+        long long off;
+        cap = row_table(i, grp, slots, need, goff, lkey, gkey, key, off);
+        acc = off >= 0 ? gacc + off : lacc + (-1 - off);
+        for (int s = gl; s < cap; s += G) {
+            key[s] = -1;
+            acc[s] = 0.0;
+        }
+        plo = max(prp[i], 0);
+        phi = max(min(prp[i + 1], pnnz), plo);
+    }
+    __syncthreads();
+    if (mi == FGPT)
+        for (int j = plo + gl; j < phi; j += G) {
+            const int c = pci[j];
+            if ((unsigned)c >= (unsigned)A.n) atomicOr(err, kErrIndex);
+            else if (tab_insert(key, cap, c) < 0) atomicOr(err, kErrTableFull);
+        }
+    __syncthreads();
+    double ahat_i = 0.0, alN = 0.0, alP = 0.0;
+    if (mi == FGPT) {
+        int lo, hi, slo, shi;
+        span(A, i, lo, hi);
+        span(S, i, slo, shi);
+        ahat_i = diag[i], alN = psum[i], alP = csum[i];
+        for (int j = slo; j < shi; ++j) {
+            const int k = S.ci[j];
+            if ((unsigned)k >= (unsigned)A.n) {
+                if (gl == 0) atomicOr(err, kErrIndex);
+                continue;
+            }
+            const int pik = group_find_last<G>(A, lo, hi, k, gl);
+            if (pik < 0) {
+                if (gl == 0) atomicOr(err, kErrStrongCol);
+                continue;
+            }
+            const double aik = A.v[pik];
+            const int mk = mark[k];
+            if (mk == CGPT) {
+                const int slot = tab_find(key, cap, k);
+                if (slot < 0) {
+                    if (gl == 0) atomicOr(err, kErrPatternCol);
+                } else if ((slot & (G - 1)) == gl) {
+                    acc[slot] += aik;
+                }
+            } else if (mk == FGPT) {
+                int klo, khi, sklo, skhi;
+                span(A, k, klo, khi);
+                span(S, k, sklo, skhi);
+                const double akk = diag[k], factor = aik / akk;
+                double aki = 0.0;
+                for (int m = klo; m < khi; ++m)
+                    if (A.ci[m] == i) {
+                        aki = A.v[m];
+                        ahat_i -= factor * aki;
+                    }
+                for (int m0 = sklo; m0 < skhi; m0 += G) {
+                    const int m = m0 + gl;
+                    int slot = -1;
+                    double prod = 0.0;
+                    if (m < skhi) {
+                        const int l = S.ci[m];
+                        if ((unsigned)l >= (unsigned)A.n) {
+                            atomicOr(err, kErrIndex);
+                        } else {
+                            int pkl = -1;   // the last entry of row k with column l
+                            for (int t = klo; t < khi; ++t)
+                                if (A.ci[t] == l) pkl = t;
+                            if (pkl < 0) {
+                                atomicOr(err, kErrStrongCol);
+                            } else if (mark[l] == CGPT) {
+                                slot = tab_find(key, cap, l);
+                                if (slot < 0) atomicOr(err, kErrPatternCol);
+                                prod = factor * A.v[pkl];
+                            }
+                        }
+                    }
+                    if (group_ballot<G>(slot >= 0, gl) == 0ull) continue;
+                    // handed to the owners in stored order: lane t's term is applied before lane t + 1's
+                    const int cnt = min(G, skhi - m0);
+                    for (int t = 0; t < cnt; ++t) {
+                        const int st = __shfl(slot, t, G);
+                        const double vt = __shfl(prod, t, G);
+                        if (st >= 0 && (st & (G - 1)) == gl) acc[st] -= vt;
+                    }
+                }
+                alN -= factor * (nsum[k] - aki + akk);
+                alP -= factor * csum[k];
+            }
+        }
+    }
+    __syncthreads();
+    if (mi == FGPT) {
+        double alpha = 0.0;
+        if (phi > plo) alpha = alN / alP;
+        for (int j = plo + gl; j < phi; j += G) {
+            const int c = pci[j];
+            const int slot = (unsigned)c < (unsigned)A.n ? tab_find(key, cap, c) : -1;
+            if (slot >= 0) pv[j] = -alpha * acc[slot] / ahat_i;
+        }
+    } else if (mi == CGPT && gl == 0) {
+        const int o = prp[i];
+        if ((unsigned)o < (unsigned)pnnz) pv[o] = 1.0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void flag_coarse(int n, const int *__restrict__ mark, int *__restrict__ flag)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i <= n) flag[i] = i < n && mark[i] == CGPT;
+}
+
+__global__ __launch_bounds__(kBlock) void renumber(int nnz, int n, const int *__restrict__ cmap, int *__restrict__ ci,
+                                                   int *__restrict__ err)
+{
+    const int q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nnz) return;
+    const int c = ci[q];
+    if ((unsigned)c < (unsigned)n) ci[q] = cmap[c];
+    else atomicOr(err, kErrIndex);
+}
+
+// interp_trunc_par, one row per lane (the sums of a row are in stored order): FILL false counts the
+// kept entries of every row into cnt, FILL true writes them at nrp
+template <bool FILL>
+__global__ __launch_bounds__(kBlock) void trunc_rows(int n, int pnnz, const int *__restrict__ prp, const int *__restrict__ pci,
+                                                     const double *__restrict__ pv, double eps, int *__restrict__ cnt,
+                                                     const int *__restrict__ nrp, int kept, int *__restrict__ nci,
+                                                     double *__restrict__ nv)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int lo = max(prp[i], 0), hi = max(min(prp[i + 1], pnnz), lo);
+    double pos_max = 0, neg_min = 0, pos_sum = 0, neg_sum = 0, pos_kept = 0, neg_kept = 0;
+    for (int k = lo; k < hi; ++k) {
+        const double v = pv[k];
+        if (v > 0) {
+            pos_sum += v;
+            pos_max = pos_max > v ? pos_max : v;
+        } else if (v < 0) {
+            neg_sum += v;
+            neg_min = neg_min < v ? neg_min : v;
+        }
+    }
+    pos_max *= eps;
+    neg_min *= eps;
+    if (!FILL) {
+        int c = 0;
+        for (int k = lo; k < hi; ++k) c += (pv[k] >= pos_max) || (pv[k] <= neg_min);
+        cnt[i] = c;
+        return;
+    }
+    const int o0 = max(nrp[i], 0), room = min(nrp[i + 1], kept) - o0;
+    int o = 0;
+    for (int k = lo; k < hi && o < room; ++k) {
+        const double v = pv[k];
+        if (v >= pos_max) {
+            nci[o0 + o++] = pci[k];
+            pos_kept += v;
+        } else if (v <= neg_min) {
+            nci[o0 + o++] = pci[k];
+            neg_kept += v;
+        }
+    }
+    const double pos_fac = pos_kept > SMALLFLOAT ? pos_sum / pos_kept : 1.0;
+    const double neg_fac = neg_kept < -SMALLFLOAT ? neg_sum / neg_kept : 1.0;
+    o = 0;
+    for (int k = lo; k < hi && o < room; ++k) {
+        const double v = pv[k];
+        if (v >= pos_max) nv[o0 + o++] = v * pos_fac;
+        else if (v <= neg_min) nv[o0 + o++] = v * neg_fac;
+    }
+}
+
+int copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind k, hipStream_t st)
+{
+    if (bytes == 0) return 0;
+    SSS_HIP(hipMemcpyAsync(dst, src, bytes, k, st));
+    SSS_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// lanes per row from the average row of S: an F row has about avg + avg^2 / 2 candidates, and a group
+// of G lanes has 8 G table slots in LDS (SSS_HIP_INTERP_LANES, tests: 1, 4, 16 or 64 whatever the rows)
+int lanes_for(int n, int snnz)
+{
+    const char *e = getenv("SSS_HIP_INTERP_LANES");
+    if (e && *e) {
+        const int g = atoi(e);
+        if (g == 1 || g == 4 || g == 16 || g == 64) return g;
+    }
+    const double avg = (double)snnz / (double)std::max(n, 1), est = avg * (1.0 + 0.5 * avg);
+    return est <= 4.0 ? 1 : est <= 16.0 ? 4 : est <= 64.0 ? 16 : 64;
+}
+
+// table slots of one group in LDS, a power of two (SSS_HIP_INTERP_LDS_SLOTS lowers it: the tests
+// reach the global tables at small shapes)
+int slots_for(int G)
+{
+    int slots = kLdsSlots / (kBlock / G);
+    const char *e = getenv("SSS_HIP_INTERP_LDS_SLOTS");
+    if (e && *e) {
+        const int want = std::max(atoi(e), 2);
+        while (slots > want) slots >>= 1;
+    }
+    return slots;
+}
+
+struct Dev {
+    hipStream_t st = nullptr;
+    std::vector<void *> mem;
+    double t_copy = 0.0, t_kern = 0.0, t_last = PhaseTimer::now();
+    bool oom = false;
+    ~Dev()
+    {
+        for (void *p : mem) dev_free(p);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    template <class T>
+    T *alloc(size_t count)
+    {
+        T *p = dev_alloc<T>(count);
+        if (p) mem.push_back(p);
+        else oom = true;
+        return p;
+    }
+    template <class T>
+    T *upload(const T *src, size_t count)
+    {
+        T *p = alloc<T>(count);
+        if (p && count && h2d(p, src, sizeof(T) * count)) oom = true;
+        return p;
+    }
+    // the time since the last call goes to the copies or to the kernels
+    void lap(bool copy)
+    {
+        const double t = PhaseTimer::now();
+        (copy ? t_copy : t_kern) += t - t_last;
+        t_last = t;
+    }
+};
+
+template <class T>
+int exclusive_sum(Dev &d, const T *in, T *out, size_t count)
+{
+    size_t bytes = 0;
+    SSS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)count, d.st));
+    void *tmp = d.alloc<char>(bytes);
+    if (!tmp) return hip_fail(hipErrorOutOfMemory, "hipMalloc(scan)", __FILE__, __LINE__);
+    SSS_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)count, d.st));
+    return 0;
+}
+
+int check_s(const SSS_IMAT *S, const int *mark)
+{
+    if (!S || !mark || S->num_rows <= 0 || !S->row_ptr) return ERROR_INPUT_PAR;
+    const int n = S->num_rows, nnz = S->row_ptr[n];
+    if (S->row_ptr[0] != 0 || nnz < 0 || (nnz > 0 && !S->col_idx)) return ERROR_INPUT_PAR;
+    // n * 64 lanes must fit the grid (2^31 - 1 blocks)
+    if ((long long)n * 64 / kBlock >= 0x7fffffffLL) return ERROR_MAT_SIZE;
+    return 0;
+}
+
+int flag_error(const char *what, int flags)
+{
+    fprintf(stderr, "[sss_hip] %s: inconsistent input (%s%s%s%s%s)\n", what, flags & kErrIndex ? " index out of range" : "",
+            flags & kErrStrongCol ? " strong column absent from the row of A" : "",
+            flags & kErrPatternCol ? " C column absent from the pattern row" : "", flags & kErrTableFull ? " table full" : "",
+            flags & kErrBound ? " row too long" : "");
+    return ERROR_DATA_STRUCTURE;
+}
+
+// What both entry points share: S and the marks uploaded, the rows' table needs and global tables.
+struct Tables {
+    Csr S{};
+    int *mark = nullptr, *need = nullptr, *ctr = nullptr, *gkey = nullptr;
+    long long *goff = nullptr, total = 0;
+    int G = 1, slots = 2, global_rows = 0;
+};
+
+unsigned grid_for(long long items) { return (unsigned)((items + kBlock - 1) / kBlock); }
+
+int read_flags(Dev &d, const Tables &t, const char *what, int *h_ctr)
+{
+    SSS_HIP(hipGetLastError());
+    if (copy_sync(h_ctr, t.ctr, sizeof(int) * 2, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    return h_ctr[0] ? flag_error(what, h_ctr[0]) : 0;
+}
+
+int make_tables(Dev &d, Tables &t, const SSS_IMAT *S, const int *mark, const int *d_prp, int pnnz, const char *what)
+{
+    const int n = S->num_rows, nnz = S->row_ptr[n];
+    t.S.n = n, t.S.nnz = nnz, t.S.v = nullptr;
+    t.S.rp = d.upload(S->row_ptr, (size_t)n + 1);
+    t.S.ci = d.upload(S->col_idx, (size_t)nnz);
+    t.mark = d.upload(mark, (size_t)n);
+    t.need = d.alloc<int>((size_t)n);
+    t.ctr = d.alloc<int>(2);
+    long long *gcap = d.alloc<long long>((size_t)n + 1);
+    t.goff = d.alloc<long long>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(interpolation tables)", __FILE__, __LINE__);
+    d.lap(true);
+    t.G = lanes_for(n, nnz);
+    t.slots = slots_for(t.G);
+    SSS_HIP(hipMemsetAsync(t.ctr, 0, sizeof(int) * 2, d.st));
+    SSS_HIP(hipMemsetAsync(gcap + n, 0, sizeof(long long), d.st));
+    hipLaunchKernelGGL(interp_bound, dim3(grid_for(n)), dim3(kBlock), 0, d.st, t.S, t.mark, d_prp, pnnz, t.slots, t.need, gcap,
+                       t.ctr);
+    if (int rc = exclusive_sum(d, gcap, t.goff, (size_t)n + 1)) return rc;
+    int h_ctr[2];
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    if (copy_sync(&t.total, t.goff + n, sizeof(long long), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    t.global_rows = h_ctr[1];
+    t.gkey = d.alloc<int>((size_t)t.total);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(global tables)", __FILE__, __LINE__);
+    d.lap(false);
+    return 0;
+}
+
+void timing_line(const char *step, const Dev &d, const Tables &t, int rows, int nnz)
+{
+    if (getenv("SSS_SETUP_TIMING"))
+        fprintf(stderr, "[setup]   standard P: device %s, %d rows, %d entries, %d lanes per row, %d rows on global tables, "
+                        "copies %.4f s, kernels %.4f s\n", step, rows, nnz, t.G, t.global_rows, d.t_copy, d.t_kern);
+}
+
+template <class T>
+struct HostArr {   // SSS_calloc'd, freed unless released into the result
+    T *p;
+    explicit HostArr(size_t count) : p((T *)SSS_calloc(std::max<size_t>(count, 1), sizeof(T))) {}
+    ~HostArr() { free(p); }
+    T *release()
+    {
+        T *q = p;
+        p = nullptr;
+        return q;
+    }
+};
+
+}  // namespace
+
+}  // namespace sss
+
+using namespace sss;
+
+// the row kernels at G lanes per row
+#define SSS_INTERP_LAUNCH(kernel, ...)                                                                             \
+    switch (G) {                                                                                                   \
+    case 1: hipLaunchKernelGGL((kernel<1, ##__VA_ARGS__>), dim3(grid_for(n)), dim3(kBlock), 0, st, a...); break;   \
+    case 4: hipLaunchKernelGGL((kernel<4, ##__VA_ARGS__>), dim3(grid_for(4LL * n)), dim3(kBlock), 0, st, a...); break;   \
+    case 16: hipLaunchKernelGGL((kernel<16, ##__VA_ARGS__>), dim3(grid_for(16LL * n)), dim3(kBlock), 0, st, a...); break; \
+    default: hipLaunchKernelGGL((kernel<64, ##__VA_ARGS__>), dim3(grid_for(64LL * n)), dim3(kBlock), 0, st, a...); break; \
+    }
+template <bool FILL, class... Args>
+static void launch_pattern(int G, hipStream_t st, int n, Args... a)
+{
+    SSS_INTERP_LAUNCH(pattern_rows, FILL)
+}
+template <class... Args>
+static void launch_weights(int G, hipStream_t st, int n, Args... a)
+{
+    SSS_INTERP_LAUNCH(weights_rows)
+}
+#undef SSS_INTERP_LAUNCH
+
+extern "C" int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P)
+{
+    if (!P) return ERROR_INPUT_PAR;
+    if (int rc = check_s(S, mark)) return rc;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    const int n = S->num_rows;
+    Dev d;
+    if (hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+    Tables t;
+    if (int rc = make_tables(d, t, S, mark, nullptr, 0, "standard pattern")) return rc;
+    int *gseq = d.alloc<int>((size_t)t.total);
+    int *cnt = d.alloc<int>((size_t)n + 1), *prp = d.alloc<int>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard pattern)", __FILE__, __LINE__);
+    SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
+    int *pci = nullptr, pnnz = 0, h_ctr[2];
+    launch_pattern<false>(t.G, d.st, n, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gseq, cnt, prp, pnnz, pci, t.ctr);
+    if (int rc = exclusive_sum(d, cnt, prp, (size_t)n + 1)) return rc;
+    if (int rc = read_flags(d, t, "standard pattern", h_ctr)) return rc;
+    if (copy_sync(&pnnz, prp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (pnnz < 0) return ERROR_MAT_SIZE;
+    pci = d.alloc<int>((size_t)pnnz);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard pattern)", __FILE__, __LINE__);
+    launch_pattern<true>(t.G, d.st, n, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gseq, cnt, prp, pnnz, pci, t.ctr);
+    if (int rc = read_flags(d, t, "standard pattern", h_ctr)) return rc;
+    d.lap(false);
+
+    // into arrays of its own first: P stays untouched if a copy fails
+    HostArr<int> rp((size_t)n + 1), ci((size_t)pnnz);
+    HostArr<double> val((size_t)pnnz);
+    if (copy_sync(rp.p, prp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(ci.p, pci, sizeof(int) * (size_t)pnnz, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    d.lap(true);
+    P->num_rows = n;
+    P->num_cols = ncoarse;
+    P->num_nnzs = pnnz;
+    P->row_ptr = rp.release();
+    P->col_idx = ci.release();
+    P->val = val.release();
+    timing_line("pattern", d, t, n, pnnz);
+    return 0;
+}
+
+extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold)
+{
+    if (!A || !P || !A->row_ptr || !P->row_ptr) return ERROR_INPUT_PAR;
+    if (int rc = check_s(S, mark)) return rc;
+    const int n = S->num_rows, annz = A->row_ptr[A->num_rows > 0 ? A->num_rows : 0];
+    if (A->num_rows != n || P->num_rows != n || A->row_ptr[0] != 0 || P->row_ptr[0] != 0) return ERROR_INPUT_PAR;
+    const int pnnz = P->row_ptr[n];
+    if (annz <= 0 || !A->col_idx || !A->val || pnnz < 0 || (pnnz > 0 && (!P->col_idx || !P->val))) return ERROR_INPUT_PAR;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    Dev d;
+    if (hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+    const int *prp = d.upload(P->row_ptr, (size_t)n + 1);
+    int *pci = d.upload(P->col_idx, (size_t)pnnz);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
+    Tables t;
+    if (int rc = make_tables(d, t, S, mark, prp, pnnz, "standard weights")) return rc;
+    Csr Ad{n, annz, nullptr, nullptr, nullptr};
+    Ad.rp = d.upload(A->row_ptr, (size_t)n + 1);
+    Ad.ci = d.upload(A->col_idx, (size_t)annz);
+    Ad.v = d.upload(A->val, (size_t)annz);
+    d.lap(true);
+    double *gacc = d.alloc<double>((size_t)t.total), *pv = d.alloc<double>((size_t)pnnz);
+    double *diag = d.alloc<double>((size_t)n), *csum = d.alloc<double>((size_t)n), *nsum = d.alloc<double>((size_t)n),
+           *psum = d.alloc<double>((size_t)n);
+    int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
+    int *cnt = d.alloc<int>((size_t)n + 1), *nrp = d.alloc<int>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
+    SSS_HIP(hipMemsetAsync(pv, 0, sizeof(double) * (size_t)std::max(pnnz, 1), d.st));
+    SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
+    hipLaunchKernelGGL(weights_sums, dim3(grid_for(n)), dim3(kBlock), 0, d.st, Ad, t.S, t.mark, diag, csum, nsum, psum, t.ctr);
+    launch_weights(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
+                   (const double *)diag, (const double *)csum, (const double *)nsum, (const double *)psum, t.ctr);
+    // the coarse numbers of the columns, then the truncation
+    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
+    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
+    if (pnnz > 0) hipLaunchKernelGGL(renumber, dim3(grid_for(pnnz)), dim3(kBlock), 0, d.st, pnnz, n, cmap, pci, t.ctr);
+    hipLaunchKernelGGL((trunc_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
+                       nrp, 0, nullptr, nullptr);
+    if (int rc = exclusive_sum(d, cnt, nrp, (size_t)n + 1)) return rc;
+    int h_ctr[2], kept = 0, ncoarse = 0;
+    if (int rc = read_flags(d, t, "standard weights", h_ctr)) return rc;
+    if (copy_sync(&kept, nrp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (kept < 0 || kept > pnnz) return ERROR_MAT_SIZE;
+    int *nci = d.alloc<int>((size_t)kept);
+    double *nv = d.alloc<double>((size_t)kept);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
+    hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
+                       nrp, kept, nci, nv);
+    if (int rc = read_flags(d, t, "standard weights", h_ctr)) return rc;
+    d.lap(false);
+
+    // into arrays of its own first: P stays untouched if a copy fails
+    HostArr<int> rp((size_t)n + 1), ci((size_t)kept);
+    HostArr<double> val((size_t)kept);
+    if (copy_sync(rp.p, nrp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(ci.p, nci, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(val.p, nv, sizeof(double) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    d.lap(true);
+    free(P->row_ptr);
+    free(P->col_idx);
+    free(P->val);
+    P->num_cols = ncoarse;
+    P->num_nnzs = kept;
+    P->row_ptr = rp.release();
+    P->col_idx = ci.release();
+    P->val = val.release();
+    timing_line("weights", d, t, n, kept);
+    return 0;
+}

@@ -18,7 +18,9 @@
  * One engine extension, off unless asked for: cs_type SSS_COARSE_PMIS (3) replaces the serial RS
  * first pass by the parallel PMIS split (pmis_split below; on the device sss_hip_pmis,
  * amg_amd/csrc/sss_pmis.hip).  No F-F cleanup runs after it; interp_type 2 is its partner.  With
- * cs_type 1 nothing here differs from the reference.
+ * cs_type 1 nothing here differs from the reference.  On large levels the standard pattern and
+ * interpolation run on the device (sss_hip_std_pattern, sss_hip_interp_std, amg_amd/csrc/sss_interp.hip):
+ * the same P bit for bit, with the code below as the fallback.
  *
  * The measure lists are kept as an array of FIFO buckets indexed by measure instead of the
  * reference's heap-allocated sorted list of list nodes with element-level linked lists
@@ -749,6 +751,24 @@ static void std_pattern(SSS_MAT *P, const SSS_IMAT *S, const SSS_IVEC *vertices,
     scratch_free(scr, T);
 }
 
+/* The host pattern on a given compacted S and marks (tests; what the device pattern is checked against). */
+int sss_std_pattern_host(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P)
+{
+    if (!S || !mark || !P || S->num_rows <= 0 || !S->row_ptr) return ERROR_INPUT_PAR;
+    SSS_IVEC v = {S->num_rows, (int *)mark};
+    std_pattern(P, S, &v, S->num_rows, ncoarse);
+    return 0;
+}
+
+/* Whether a level with nnz nonzeros in A takes the device pattern and weights: a device is present,
+ * SSS_SETUP_GPU_INTERP is not 0 and nnz is at least SSS_SETUP_GPU_INTERP_MIN (include/sss_hip.h). */
+static int interp_on_device(int nnz)
+{
+    const char *g = getenv("SSS_SETUP_GPU_INTERP"), *gm = getenv("SSS_SETUP_GPU_INTERP_MIN");
+    const int gpu_min = (gm && *gm) ? atoi(gm) : SSS_SETUP_GPU_INTERP_MIN_DEFAULT;
+    return !(g && g[0] == '0') && nnz >= gpu_min && sss_hip_device_count() > 0;
+}
+
 int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
 {
     int ncoarse = 0;
@@ -774,7 +794,13 @@ int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS
                     t1 - t0, split, t2 - t1, t3 - t2, SSS_get_time() - t3);
     } else if (pars->interp_type == intERP_STD) {   /* no F-F cleanup before the standard pattern */
         const double t3 = SSS_get_time();
-        std_pattern(P, S, vertices, A->num_rows, ncoarse);
+        /* the device pattern is the host's, array for array; on any error code the host builds it */
+        if (!(interp_on_device(A->num_nnzs) && sss_hip_std_pattern(S, vertices->d, ncoarse, P) == 0)) {
+            std_pattern(P, S, vertices, A->num_rows, ncoarse);
+            if (timing)
+                fprintf(stderr, "[setup]   standard P: host pattern %.4f s, %d rows, %d entries\n", SSS_get_time() - t3,
+                        P->num_rows, P->num_nnzs);
+        }
         if (timing)
             fprintf(stderr, "[setup]   coarsen: strength %.3f s, %s split %.3f s, standard P pattern %.3f s\n", t1 - t0,
                     split, t2 - t1, SSS_get_time() - t3);
@@ -1002,6 +1028,11 @@ static void interp_STD(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, 
     const int *mark = vertices->d;
     const int *ia = A->row_ptr, *ja = A->col_idx;
     const double *a = A->val;
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const double t0 = SSS_get_time();
+    /* the device weights (renumbered, truncated) are the host's bit for bit; on any error code P is
+     * untouched and the host computes them */
+    if (interp_on_device(A->num_nnzs) && sss_hip_interp_std(A, S, mark, P, pars->trunc_threshold) == 0) return;
     double *csum = (double *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(double));
     double *psum = (double *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(double));
     double *nsum = (double *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(double));
@@ -1092,6 +1123,9 @@ static void interp_STD(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, 
     free(diag);
     /* step 3 */
     SSS_amg_interp_trunc(P, pars);
+    if (timing)
+        fprintf(stderr, "[setup]   standard P: host weights %.4f s, %d rows, %d entries\n", SSS_get_time() - t0, P->num_rows,
+                P->num_nnzs);
 }
 
 void SSS_amg_interp(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)

@@ -123,6 +123,30 @@ int sss_hip_pmis(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds);
  * small levels, and what the device split is tested against.  0 or an error code. */
 int sss_pmis_host(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds);
 
+/* The standard interpolation (interp_type intERP_STD) on the GPU, bit for bit the host
+ * result.  sss_hip_std_pattern builds the pattern of form_P_pattern_std from a compacted S and the
+ * marks: P gets row_ptr, col_idx (fine numbering, the host's discovery order), val zeroed, num_cols =
+ * ncoarse.  sss_hip_interp_std computes interp_STD on such a pattern: the weights, the coarse
+ * renumbering of the columns and the truncation; P's arrays are freed and replaced.  Each call uploads
+ * what it reads and downloads what it produces; the output arrays are SSS_calloc'd.  Both return 0, or
+ * an error code with P untouched (no device, no rows, no memory, a failed copy, input the kernels found
+ * inconsistent: an index out of range, a strong column absent from the row of A, a C column absent
+ * from the pattern row); the setup then runs the host code.  SSS_HIP_INTERP_LANES = 1, 4, 16 or 64
+ * forces the lanes per row, SSS_HIP_INTERP_LDS_SLOTS lowers the per-row table kept in LDS (longer
+ * rows use a table in global memory inside the same call).  Under SSS_SETUP_TIMING each call prints
+ * one stderr line: lanes per row, rows on global tables, seconds of copies and of kernels.
+ * The setup uses both, when a device is present, for levels whose A has at least
+ * SSS_SETUP_GPU_INTERP_MIN nonzeros (default SSS_SETUP_GPU_INTERP_MIN_DEFAULT = 10^7: measured at 7-pt
+ * 400^3 with PMIS marks, pattern and weights together cost about 4.4 ms + 1.4 ns per nonzero of A on the
+ * device, copies included, and about 5 ns per nonzero on the host on 16 threads; they cross near 1.2 * 10^6,
+ * rounded up to a power of ten); SSS_SETUP_GPU_INTERP=0 keeps both on the host. */
+#define SSS_SETUP_GPU_INTERP_MIN_DEFAULT 10000000
+int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P);
+int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold);
+/* The pattern on the host (OpenMP, row-parallel): what the setup runs without a device or on small
+ * levels, and what the device pattern is tested against.  0 or an error code. */
+int sss_std_pattern_host(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P);
+
 /* Progress hook of the setup (amg_amd/host/sss_setup.c): hook(ctx, mg, done, 0) once levels
  * 0 .. done-1 are final and none of them is the coarsest; hook(ctx, mg, num_levels - 1, 1) at
  * the end. */
