@@ -1769,12 +1769,20 @@ extern "C" void sss_hip_host_cache_clear(void) { prepared().clear(); }
 extern "C" int sss_hip_host_spmv(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
                                  double *y, int cap)
 {
+    return sss_hip_host_spmv_order(op, alpha, A, x, b, y, cap, 0);   // always the reference's summation order here
+}
+
+extern "C" int sss_hip_host_spmv_order(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
+                                       double *y, int cap, int sum_order)
+{
     if (sss_hip_device_count() <= 0) return ERROR_MISC;
     sss_hip_opts o;
-    sss_hip_opts_default(&o);   // SSS_HIP_SORTED_TILES; always the reference's summation order here
+    sss_hip_opts_default(&o);   // SSS_HIP_SORTED_TILES
+    o.sum_order = sum_order == 1 ? 1 : 0;
+    const int order = o.sum_order == 1 ? kEncFreeOrder : 0;
     // rectangular operators (P, R) may take the dictionary ELL, as the hierarchy's restrictions
-    int enc = level_encoding(o) & (kEncSortedTiles | kEncDict);
-    if (A->num_rows != A->num_cols) enc = restriction_encoding(o) & (kEncSortedTiles | kEncEll);
+    int enc = level_encoding(o) & (kEncSortedTiles | kEncDict | order);
+    if (A->num_rows != A->num_cols) enc = restriction_encoding(o) & (kEncSortedTiles | kEncEll | order);
     auto M = prepared().get<HostCSR>(matrix_key(*A, 0x5350ull ^ ((unsigned long long)enc << 8)), [&] {
         auto m = std::make_shared<HostCSR>();
         return devcsr_upload(m->d, *A, -1, enc) ? nullptr : m;

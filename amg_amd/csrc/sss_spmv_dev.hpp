@@ -1024,17 +1024,21 @@ __device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__re
         }
 }
 
-// The same sums with the lane's accumulators in LDS (DevCSR::mg_acc): acc is this wave's
-// [S * G][64] doubles, accumulator a = segment * G + row, lane l owning column l of each.  Every
-// product is added to its own accumulator only (one LDS fp64 add per entry) instead of being
-// offered to all S * G register accumulators (a compare, two selects and an add each).
+// The same sums with the lane's accumulators in LDS (DevCSR::mg_acc): every product is added to
+// its own accumulator only (one LDS fp64 add per entry) instead of being offered to all S * G
+// register accumulators (a compare, two selects and an add each).  A wave's accumulators are
+// [.][64] doubles, lane l owning column l of each, the accumulator of key k = segment << 3 | row
+// at k * 64 doubles from the wave's base (merged_acc_base), so an entry's LDS address is two
+// instructions from its key word.  G = 4 with two segments uses the keys 0 ... 3 and 8 ... 11:
+// waves 2 v and 2 v + 1 share 16 slots, the second shifted by 4, which fills the gaps.
 // The sums keep their bits: in the register form an accumulator receives its own products in
 // increasing position and +0.0 for every foreign entry; s + 0.0 == s for every s but -0.0, and an
 // accumulator is never -0.0 (it starts at +0.0, and (+0.0) + (-0.0) = +0.0), so dropping the
 // foreign adds changes nothing.  A lane's LDS operations complete in issue order and no lane
-// touches another's column, so the order of a lane's own adds is the register form's; the
-// butterfly and the W-combine are unchanged.  The stride between accumulators is 512 B: the bank
-// depends on the lane only, 16 consecutive lanes cover the 32 banks once (no conflicts).
+// touches another's column before the tree (merged_tree_lds), so the order of a lane's own adds
+// is the register form's; the tree adds the butterfly's pairs and the W-combine is unchanged.  The
+// stride between accumulators is 512 B: the bank depends on the lane only, 16 consecutive lanes
+// cover the 32 banks once (no conflicts).
 // A wave takes its entries in batches of up to U chunks of 64; the bounds are the same in every
 // lane, so the batch's chunk count C is a scalar and each count has its own straight-line code
 // (merged_batch_lds<C>): one base pointer plus constant offsets, every key and value load, then
@@ -1044,6 +1048,23 @@ __device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__re
 constexpr int kMergeAccDoubles = 64;   // per accumulator and wave
 template <int S>
 constexpr int kMergeLdsChunks = S == 2 ? 6 : 8;   // chunks per batch (U changes no sum)
+// key = segment << 3 | row with row < G by construction (build_merged); the mask keeps any key
+// inside the wave's accumulators
+template <int G, int S>
+constexpr unsigned kMergeKeyMask = S == 2 ? (8u | (unsigned)(G - 1)) : (unsigned)(G - 1);
+// (accumulator a = segment * G + row  ->  its key)
+template <int G, int S>
+__device__ __forceinline__ constexpr int merged_acc_key(int a)
+{
+    return S == 2 ? (a / G) << 3 | (a % G) : a;
+}
+// first double of wave w's accumulators in a block's 4 * S * G * kMergeAccDoubles
+template <int G, int S>
+__device__ __forceinline__ int merged_acc_base(int w)
+{
+    if (S == 2 && G == 4) return ((w >> 1) * 16 + (w & 1) * 4) * kMergeAccDoubles;
+    return w * (S * G * kMergeAccDoubles);
+}
 template <int G, int S, int C, class Fetch>
 __device__ __forceinline__ void merged_batch_lds(const unsigned *__restrict__ pk, const double *__restrict__ pv,
                                                  int last_n, Fetch fetch, double *mine)
@@ -1062,13 +1083,11 @@ __device__ __forceinline__ void merged_batch_lds(const unsigned *__restrict__ pk
     for (int t = 0; t < C; ++t) xv[t] = fetch((int)(q[t] >> kMergeShift));
 #pragma unroll
     for (int t = 0; t < C; ++t) {
-        // key = segment << 3 | row with row < G by construction (build_merged); the masks keep any
-        // key inside the wave's S * G accumulators
-        const unsigned key = q[t] & ((1u << kMergeShift) - 1);
-        const unsigned slot = S == 2 ? (key >> 3) * G + (key & (G - 1)) : key & (G - 1);
+        static_assert(kMergeKeyMask<G, S> < (1u << kMergeShift), "key bits");
+        const unsigned key = q[t] & kMergeKeyMask<G, S>;
         double p = a[t] * xv[t];
         if (t == C - 1) p = lane < last_n ? p : 0.0;
-        atomicAdd(&mine[slot * kMergeAccDoubles], p);   // ds_add_f64, no return value
+        atomicAdd(&mine[key * kMergeAccDoubles], p);   // ds_add_f64, no return value
     }
 }
 // (nch is the same in every lane: a chain of scalar branches)
@@ -1084,16 +1103,45 @@ __device__ __forceinline__ void merged_batch_dispatch(int nch, const unsigned *_
         else merged_batch_dispatch<G, S, C - 1>(nch, pk, pv, last_n, fetch, mine);
     }
 }
+// The xor-butterfly's sums, as its lane 0 holds them, of the wave's S * G accumulators, taken out
+// of LDS.  Lane 0's value after the butterfly's step at distance off is built from the lanes
+// l < off alone, and there l ^ off == l + off: each step is v[l] += v[l + off] for l < off.  The
+// LP = 64 / (S * G) lanes a * LP ... a * LP + LP - 1 take accumulator a: lane i of them reads the
+// elements i + LP m, runs the steps at distance 32 ... LP on its own registers (element i + LP m
+// pairs with i + LP (m + off / LP)) and the steps LP / 2 ... 1 across the LP lanes.  Every step
+// adds the butterfly's pairs, the lower element on the left as there, so the sums keep their bits.
+// out[a] = the sum of accumulator a (written by lane a * LP).
+template <int G, int S>
+__device__ __forceinline__ void merged_tree_lds(const double *acc, double *out)
+{
+    constexpr int NA = S * G, LP = 64 / NA;
+    static_assert(NA >= 2 && NA <= 32 && LP * NA == 64, "accumulators per wave");
+    const int lane = threadIdx.x & 63, a = lane / LP, i = lane % LP;
+    const double *col = acc + merged_acc_key<G, S>(a) * kMergeAccDoubles + i;
+    wave_sync();   // the other lanes' adds: a wave's LDS operations complete in issue order
+    double v[NA];
+#pragma unroll
+    for (int m = 0; m < NA; ++m) v[m] = col[LP * m];
+#pragma unroll
+    for (int h = NA / 2; h > 0; h >>= 1)
+#pragma unroll
+        for (int m = 0; m < h; ++m) v[m] += v[m + h];
+    double s = v[0];
+#pragma unroll
+    for (int off = LP / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (i == 0) out[a] = s;
+}
+// acc: the wave's accumulators; out[segment * G + row] = the wave's sum
 template <int G, int S, class Fetch>
 __device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *__restrict__ mk,
                                                 const double *__restrict__ mv, Fetch fetch, double *acc,
-                                                double (&s0)[G], double (&s1)[G])
+                                                double *out)
 {
     constexpr int U = kMergeLdsChunks<S>;
     const int lane = threadIdx.x & 63;
     double *mine = acc + lane;
 #pragma unroll
-    for (int a = 0; a < S * G; ++a) mine[a * kMergeAccDoubles] = 0.0;
+    for (int a = 0; a < S * G; ++a) mine[merged_acc_key<G, S>(a) * kMergeAccDoubles] = 0.0;
     // (wave-uniform: scalar loop control and base pointers)
     k1 = __builtin_amdgcn_readfirstlane(k1);
     for (int kb = __builtin_amdgcn_readfirstlane(k0); kb < k1; kb += 64 * U) {
@@ -1102,18 +1150,7 @@ __device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *
         const double *pv = mv + kb;
         merged_batch_dispatch<G, S, U>(nch, pk, pv, last_n, fetch, mine);
     }
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-        s0[u] = mine[u * kMergeAccDoubles];
-        s1[u] = S == 2 ? mine[(G + u) * kMergeAccDoubles] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s0[u] += __shfl_xor(s0[u], off, 64);
-            if (S == 2) s1[u] += __shfl_xor(s1[u], off, 64);
-        }
+    merged_tree_lds<G, S>(acc, out);
 }
 
 // Merged groups per 256-thread workgroup: W waves per group (W = 1, 2 or 4, DevCSR::mg_W), so
@@ -1123,40 +1160,47 @@ __device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *
 // red: 8G doubles of LDS.  Must be reached by every thread of the block.
 // LDSACC: the lanes' accumulators in acc, 4 * S * G * kMergeAccDoubles doubles of LDS
 // (merged_sums_lds; acc unused otherwise).
+// (W is a power of two: its divisions are shifts; the wave index is a scalar, so the group's bounds
+// are scalar loads)
 template <int G, int S, bool LDSACC, class Fetch>
 __device__ __forceinline__ bool merged_block(const int *__restrict__ gp, int ng, int W, const unsigned *__restrict__ mk,
                                              const double *__restrict__ mv, Fetch fetch, double *red, double *acc,
                                              int &g_out, int &u_out, double &t0, double &t1)
 {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, gpb = 4 / W;
-    const int g = xcd_bid() * gpb + w / W, part = w % W;
-    double s0[G], s1[G];
-    if (g < ng) {
-        const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + W - 1) / W;
-        if constexpr (LDSACC)
-            merged_sums_lds<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch,
-                                  acc + w * (S * G * kMergeAccDoubles), s0, s1);
-        else
-            merged_sums<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch, s0, s1);
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int wsh = W >= 4 ? 2 : W >= 2 ? 1 : 0, gpb = 4 >> wsh;
+    const int g = xcd_bid() * gpb + (w >> wsh), part = w & ((1 << wsh) - 1);
+    // the wave's sums: red[(w * 2 + segment) * G + row]
+    if (LDSACC && g < ng) {
+        const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + (1 << wsh) - 1) >> wsh;
+        merged_sums_lds<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch,
+                              acc + merged_acc_base<G, S>(w), red + (w * 2) * G);
     } else {
+        double s0[G], s1[G];
+        if (g < ng) {
+            const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + (1 << wsh) - 1) >> wsh;
+            merged_sums<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch, s0, s1);
+        } else {
 #pragma unroll
-        for (int u = 0; u < G; ++u) s0[u] = 0.0, s1[u] = 0.0;
-    }
-    if (lane == 0)
-#pragma unroll
-        for (int u = 0; u < G; ++u) {
-            red[(w * 2) * G + u] = s0[u];
-            if (S == 2) red[(w * 2 + 1) * G + u] = s1[u];
+            for (int u = 0; u < G; ++u) s0[u] = 0.0, s1[u] = 0.0;
         }
+        if (lane == 0)
+#pragma unroll
+            for (int u = 0; u < G; ++u) {
+                red[(w * 2) * G + u] = s0[u];
+                if (S == 2) red[(w * 2 + 1) * G + u] = s1[u];
+            }
+    }
     __syncthreads();
     const int t = threadIdx.x;
     if (t >= gpb * G) return false;
     const int gi = t / G, u = t % G, gg = xcd_bid() * gpb + gi;
     if (gg >= ng) return false;
-    double a0 = red[((gi * W) * 2) * G + u], a1 = S == 2 ? red[((gi * W) * 2 + 1) * G + u] : 0.0;
-    for (int v = 1; v < W; ++v) {
-        a0 += red[((gi * W + v) * 2) * G + u];
-        if (S == 2) a1 += red[((gi * W + v) * 2 + 1) * G + u];
+    const int w0 = gi << wsh;   // the group's first wave
+    double a0 = red[(w0 * 2) * G + u], a1 = S == 2 ? red[(w0 * 2 + 1) * G + u] : 0.0;
+    for (int v = 1; v < (1 << wsh); ++v) {
+        a0 += red[((w0 + v) * 2) * G + u];
+        if (S == 2) a1 += red[((w0 + v) * 2 + 1) * G + u];
     }
     g_out = gg, u_out = u, t0 = a0, t1 = a1;
     return true;

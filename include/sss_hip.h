@@ -243,6 +243,11 @@ int sss_hip_spmv(const sss_hip_spmv_plan *p, int op, double alpha, const int *d_
  * SSS_blas_mv_* / smoother / coarse-solve entry points. */
 int sss_hip_host_spmv(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
                       double *y, int cap);
+/* The same product in the summation order sss_hip_opts.sum_order names (0: the reference's, as
+ * sss_hip_host_spmv; 1: the free order of the long-row kernels, deterministic but not the
+ * reference's bits). */
+int sss_hip_host_spmv_order(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
+                            double *y, int cap, int sum_order);
 int sss_hip_host_smooth(const SSS_SMTR *s, int post);
 /* One orthogonalisation step of sss_hip_fgmres on host data, through the same kernels: V holds k
  * columns of n doubles back to back; w is orthogonalised against them in place (not normalised),

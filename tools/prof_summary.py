@@ -51,7 +51,7 @@ def main():
     lines = [a.header] if a.header else []
     for (n, g), ds in sorted(shape.items(), key=lambda kv: -sum(kv[1])):
         lines.append(f"{n[:44]:44s}  workgroups={g:9d} calls={len(ds):5d} avg_us={sum(ds)/len(ds)/1e3:10.1f} "
-                     f"total_ms={sum(ds)/1e6:9.2f}")
+                     f"total_ms={sum(ds)/1e6:9.2f} min_us={min(ds)/1e3:8.1f} max_us={max(ds)/1e3:8.1f}")
     txt = "\n".join(lines) + "\n"
     if a.shapes:
         with open(a.shapes, "w") as f:
