@@ -117,6 +117,7 @@ ABI_SYMBOLS = [
     "SSS_amg_save", "SSS_amg_load",
     "sss_hip_coarse_solve", "sss_hip_smooth", "sss_hip_sync", "sss_hip_level_info_get", "sss_hip_num_levels", "sss_hip_tail_from",
     "sss_hip_cycle_launches", "sss_hip_cycle_bytes",
+    "sss_hip_merged_narrow", "sss_hip_merged_key_stats", "sss_hip_merged_keys_get",
     "sss_hip_spmv_plan_create", "sss_hip_spmv_plan_destroy", "sss_hip_spmv", "sss_hip_host_spmv", "sss_hip_host_spmv_order",
     "sss_hip_host_smooth", "sss_hip_host_coarse_solve", "sss_hip_host_cache_clear", "sss_hip_time_level0_spmv", "sss_hip_time_iterations",
     "sss_hip_time_level0_spmv_csr", "sss_hip_time_levels", "sss_hip_dist_time_tail_levels",
@@ -211,6 +212,11 @@ def _declare(lib):
         "sss_hip_tail_from": (C.c_int, [C.c_void_p]),
         "sss_hip_cycle_launches": (C.c_int, [C.c_void_p]),
         "sss_hip_cycle_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
+        "sss_hip_merged_narrow": (C.c_int, [C.c_void_p, C.c_longlong, _int_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_longlong, P(C.c_longlong), C.c_void_p, C.c_longlong,
+                                            P(C.c_longlong), P(C.c_longlong)]),
+        "sss_hip_merged_key_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_longlong)]),
+        "sss_hip_merged_keys_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
         "sss_hip_host_spmv": (C.c_int, [C.c_int, C.c_double, P(SSS_MAT), _dbl_p, _dbl_p, _dbl_p, C.c_int]),
         "sss_hip_host_spmv_order": (C.c_int, [C.c_int, C.c_double, P(SSS_MAT), _dbl_p, _dbl_p, _dbl_p, C.c_int, C.c_int]),
         "sss_hip_host_smooth": (C.c_int, [P(SSS_SMTR), C.c_int]),

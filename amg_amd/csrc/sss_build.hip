@@ -75,6 +75,97 @@ int segmented_sort(const unsigned *kin, unsigned *kout, const double *vin, doubl
     return 0;
 }
 
+// Narrow keys of a sorted merged key list (DevCSR::mg_k16 / mg_d; the host's merged_narrow bit for
+// bit): one wave per share (group s / W, part s % W), a chunk of 64 keys per step.  elen[s] = the
+// share's entries if one of its chunks is wide (the share then keeps 32-bit keys), else 0; cnt as
+// DevCSR::mg_cnt.  desc is zero-filled by the caller.
+struct ShareSpan {
+    int a, e;         // entries [a, e)
+    long long d0;     // first descriptor
+};
+__device__ __forceinline__ ShareSpan share_span(long long s, int W, const int *__restrict__ gp)
+{
+    const int g = (int)(s / W), part = (int)(s % W);
+    const long long k0 = gp[g], len = gp[g + 1] - k0, per = (len + W - 1) / W;
+    ShareSpan sp;
+    sp.a = (int)(k0 + min(len, part * per));
+    sp.e = (int)(k0 + min(len, (part + 1) * per));
+    sp.d0 = (sp.a >> 6) + (long long)g * W + part;
+    return sp;
+}
+__global__ __launch_bounds__(kBlock) void narrow_chunks(int ng, int W, int two, const int *__restrict__ gp,
+                                                        const unsigned *__restrict__ key,
+                                                        unsigned short *__restrict__ k16, int4 *__restrict__ desc,
+                                                        int *__restrict__ elen, unsigned long long *__restrict__ cnt)
+{
+    constexpr int kSpan = 1 << kMergeDeltaBits;
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (s >= (long long)ng * W) return;
+    const ShareSpan sp = share_span(s, W, gp);
+    unsigned c[4] = {0, 0, 0, 0};
+    bool wide = false;
+    int ch = 0;
+    for (int kb = sp.a; kb < sp.e; kb += 64, ++ch) {
+        const int m = min(64, sp.e - kb);
+        const bool live = lane < m;
+        const unsigned q = live ? key[kb + lane] : 0u;
+        const int col = (int)(q >> kMergeShift);
+        const int prev = __shfl_up(col, 1, 64);
+        const int w = (live && lane >= 1) ? col - prev : 0;   // the gap before this lane (sorted: >= 0)
+        // the widest gap, the lowest lane on ties
+        unsigned long long best = ((unsigned long long)(unsigned)w << 6) | (unsigned)(63 - lane);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_xor(best, off, 64);
+            best = o > best ? o : best;
+        }
+        int split = (best >> 6) > 0 ? 63 - (int)(best & 63) : 64;
+        const int first = __shfl(col, 0, 64), last = __shfl(col, m - 1, 64);
+        int lo = first, hi = first, kind;
+        if (last - first < kSpan) {
+            kind = 1, split = 64;
+        } else {
+            hi = __shfl(col, split, 64);
+            const int below = __shfl(col, split - 1, 64) - first;
+            kind = (below < kSpan && last - hi < kSpan) ? 2 : 3;
+        }
+        ++c[0], ++c[kind];
+        unsigned short k = 0;
+        int4 d = make_int4(0, 0, 64, -1);
+        if (kind == 3) {
+            wide = true;
+        } else {
+            d = make_int4(lo, hi, split, -1);
+            const unsigned acc = two ? ((q >> 1) & 4u) | (q & 3u) : q & 7u;
+            k = (unsigned short)((unsigned)(col - (lane < split ? lo : hi)) << 3 | acc);
+        }
+        if (live) k16[kb + lane] = k;
+        if (lane == 0) desc[sp.d0 + ch] = d;
+    }
+    if (lane == 0) {
+        elen[s] = wide ? sp.e - sp.a : 0;
+        for (int i = 0; i < 4; ++i)
+            if (c[i]) atomicAdd(&cnt[i], (unsigned long long)c[i]);
+        if (wide) atomicAdd(&cnt[4], (unsigned long long)ch);
+    }
+}
+// the escaped shares' 32-bit keys at eoff[s] (the exclusive sum of elen), and their chunks' positions
+__global__ __launch_bounds__(kBlock) void narrow_escape(int ng, int W, const int *__restrict__ gp,
+                                                        const unsigned *__restrict__ key, const int *__restrict__ eoff,
+                                                        int4 *__restrict__ desc, unsigned *__restrict__ ke)
+{
+    const int lane = threadIdx.x & 63;
+    const long long s = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (s >= (long long)ng * W) return;
+    const int o = eoff[s];
+    if (eoff[s + 1] == o) return;
+    const ShareSpan sp = share_span(s, W, gp);
+    const int m = sp.e - sp.a;
+    for (int i = lane; i < m; i += 64) ke[o + i] = key[sp.a + i];
+    for (int c = lane; c < (m + 63) >> 6; c += 64) desc[sp.d0 + c].w = o + 64 * c;
+}
+
 int upload_seg(const int *h_seg, int n, int **d_seg)
 {
     *d_seg = nullptr;
@@ -82,6 +173,59 @@ int upload_seg(const int *h_seg, int n, int **d_seg)
     *d_seg = dev_alloc<int>((size_t)n);
     if (!*d_seg) return hip_fail(hipErrorOutOfMemory, "hipMalloc(seg)", __FILE__, __LINE__);
     return h2d(*d_seg, h_seg, sizeof(int) * (size_t)n);
+}
+
+// d.mg_k16 / mg_d / mg_ke from the sorted 32-bit keys (d.mg_gp, mg_ng, mg_W, mg_two set)
+int merged_narrow_device(DevCSR &d, const unsigned *sorted)
+{
+    const int ng = d.mg_ng, W = d.mg_W;
+    const long long ns = (long long)ng * W, nd = merged_desc_slots(d.nnz, ng, W);
+    d.mg_nd = nd;
+    d.mg_k16 = dev_alloc<unsigned short>((size_t)d.nnz);
+    d.mg_d = dev_alloc<int4>((size_t)nd);
+    int *elen = dev_alloc<int>((size_t)ns + 1), *eoff = dev_alloc<int>((size_t)ns + 1);
+    unsigned long long *cnt = dev_alloc<unsigned long long>(5);
+    void *tmp = nullptr;
+    int rc = (!d.mg_k16 || !d.mg_d || !elen || !eoff || !cnt) ? hip_fail(hipErrorOutOfMemory, "hipMalloc(narrow)", __FILE__, __LINE__) : 0;
+    auto check = [&](hipError_t e, const char *what) {
+        if (!rc && e != hipSuccess) rc = hip_fail(e, what, __FILE__, __LINE__);
+    };
+    if (!rc) {
+        check(hipMemsetAsync(d.mg_d, 0, sizeof(int4) * (size_t)nd, nullptr), "hipMemset(narrow)");
+        check(hipMemsetAsync(elen, 0, sizeof(int) * ((size_t)ns + 1), nullptr), "hipMemset(narrow)");
+        check(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * 5, nullptr), "hipMemset(narrow)");
+    }
+    const unsigned grid = (unsigned)((ns + kBlock / 64 - 1) / (kBlock / 64));
+    int total = 0;
+    if (!rc && ns > 0) {
+        hipLaunchKernelGGL(narrow_chunks, dim3(grid), dim3(kBlock), 0, nullptr, ng, W, d.mg_two ? 1 : 0, d.mg_gp, sorted,
+                           d.mg_k16, d.mg_d, elen, cnt);
+        check(hipGetLastError(), "narrow_chunks");
+        size_t tb = 0;
+        check(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, elen, eoff, (int)(ns + 1), nullptr), "scan(narrow)");
+        check(hipMalloc(&tmp, std::max<size_t>(tb, 1)), "hipMalloc(narrow)");
+        if (!rc) check(hipcub::DeviceScan::ExclusiveSum(tmp, tb, elen, eoff, (int)(ns + 1), nullptr), "scan(narrow)");
+        if (!rc) check(hipMemcpy(&total, eoff + ns, sizeof(int), hipMemcpyDeviceToHost), "hipMemcpy(narrow)");
+    }
+    if (!rc) {
+        unsigned long long c[5] = {};
+        check(hipMemcpy(c, cnt, sizeof(c), hipMemcpyDeviceToHost), "hipMemcpy(narrow)");
+        for (int i = 0; i < 5; ++i) d.mg_cnt[i] = (long long)c[i];
+        d.mg_ne = total;
+        d.mg_ke = dev_alloc<unsigned>((size_t)std::max(total, 1));
+        if (!d.mg_ke) rc = hip_fail(hipErrorOutOfMemory, "hipMalloc(narrow)", __FILE__, __LINE__);
+    }
+    if (!rc && total > 0) {
+        hipLaunchKernelGGL(narrow_escape, dim3(grid), dim3(kBlock), 0, nullptr, ng, W, d.mg_gp, sorted, eoff, d.mg_d,
+                           d.mg_ke);
+        check(hipGetLastError(), "narrow_escape");
+    }
+    check(hipStreamSynchronize(nullptr), "narrow");   // `sorted` is freed by the caller
+    (void)hipFree(tmp);
+    dev_free(elen);
+    dev_free(eoff);
+    dev_free(cnt);
+    return rc;
 }
 
 }  // namespace
@@ -97,13 +241,14 @@ int merged_build_device(DevCSR &d, const int *h_seg)
 {
     const int n = d.n, G = d.mg_G, ng = (n + G - 1) / G;
     d.mg_ng = ng;
+    const bool narrow = merged_key16_ok(d);
     d.mg_gp = dev_alloc<int>((size_t)ng + 1);
-    d.mg_k = dev_alloc<unsigned>((size_t)d.nnz);
+    unsigned *sorted = dev_alloc<unsigned>((size_t)d.nnz);   // the 32-bit keys: mg_k, or scratch of the narrowing
     d.mg_v = dev_alloc<double>((size_t)d.nnz);
     unsigned *key = dev_alloc<unsigned>((size_t)d.nnz);
     int *dseg = nullptr;
-    int rc = (!d.mg_gp || !d.mg_k || !d.mg_v || !key) ? hip_fail(hipErrorOutOfMemory, "hipMalloc(merged)", __FILE__, __LINE__)
-                                                        : upload_seg(h_seg, n, &dseg);
+    int rc = (!d.mg_gp || !sorted || !d.mg_v || !key) ? hip_fail(hipErrorOutOfMemory, "hipMalloc(merged)", __FILE__, __LINE__)
+                                                       : upload_seg(h_seg, n, &dseg);
     if (!rc) {
         hipLaunchKernelGGL(group_bounds, dim3((ng + kBlock) / kBlock), dim3(kBlock), 0, nullptr, n, G, ng, d.rp, d.mg_gp);
         if (n > 0)
@@ -112,9 +257,15 @@ int merged_build_device(DevCSR &d, const int *h_seg)
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "merged_keys", __FILE__, __LINE__);
     }
-    if (!rc) rc = segmented_sort(key, d.mg_k, d.v, d.mg_v, d.nnz, ng, d.mg_gp, nullptr);
+    if (!rc) rc = segmented_sort(key, sorted, d.v, d.mg_v, d.nnz, ng, d.mg_gp, nullptr);
     dev_free(key);
     dev_free(dseg);
+    if (!narrow || rc) {
+        d.mg_k = sorted;
+        return rc;
+    }
+    rc = merged_narrow_device(d, sorted);
+    dev_free(sorted);
     return rc;
 }
 

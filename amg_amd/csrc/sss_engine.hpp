@@ -264,8 +264,41 @@ struct DevCSR {
     bool mg_two = false;       // two-segment rows
     unsigned *mg_k = nullptr;
     double *mg_v = nullptr;
+    // Narrow keys (SSS_HIP_MERGE_KEY16, merged_narrow): the same entries in the same order with a
+    // 16-bit key  column delta << 3 | accumulator  (accumulator: segment << 2 | row with two segments,
+    // else row) and one descriptor per chunk of 64 entries counted from each wave's share:
+    // {base_lo, base_hi, split, esc} -- the entry at lane l of the chunk has column
+    // (l < split ? base_lo : base_hi) + delta.  A share with a chunk that fits neither one nor two
+    // bases keeps 32-bit keys: esc >= 0 is the chunk's first key in mg_ke (the share's keys are
+    // contiguous there).  Chunk c of share `part` of group g is descriptor
+    // ((first entry of the share) >> 6) + g * mg_W + part + c.  mg_k is then null.
+    unsigned short *mg_k16 = nullptr;
+    int4 *mg_d = nullptr;
+    unsigned *mg_ke = nullptr;
+    long long mg_nd = 0, mg_ne = 0;   // descriptor slots, escaped keys
+    long long mg_cnt[5] = {};         // chunks: all, one base, two bases, wide, stored with 32-bit keys
 };
+// the keys of a merged copy as its kernels take them: k (32-bit), or k16 / d / ke (narrow)
+struct MergedKeys {
+    const unsigned *k;
+    const unsigned short *k16;
+    const int4 *d;
+    const unsigned *ke;
+};
+__host__ __device__ inline MergedKeys merged_keys_of(const DevCSR &A) { return MergedKeys{A.mg_k, A.mg_k16, A.mg_d, A.mg_ke}; }
 constexpr int kMergeShift = 4;           // segment + row-in-group bits of a merged entry (G <= 8)
+constexpr int kMergeDeltaBits = 13;      // column delta bits of a narrow merged key
+// descriptor slots of a narrow merged copy (see DevCSR::mg_d)
+inline long long merged_desc_slots(long long nnz, int ng, int W) { return (nnz >> 6) + (long long)ng * W + 1; }
+// Narrow keys, descriptors and escape list of a sorted 32-bit merged key list (host; both builders'
+// reference, sss_hip_merged_narrow).  k16: nnz, desc: merged_desc_slots() x 4 ints, zero-filled
+// here; esc receives the escaped shares' keys in share order; cnt as DevCSR::mg_cnt.
+void merged_narrow(const unsigned *keys, long long nnz, const int *gp, int ng, bool two, int W, unsigned short *k16,
+                   int *desc, std::vector<unsigned> &esc, long long cnt[5]);
+// the switch (read per upload; tests compare both ways)
+bool merge_key16_on();
+// (three accumulator bits: G = 8 with two segments, never selected by devcsr_upload, keeps 32-bit keys)
+inline bool merged_key16_ok(const DevCSR &d) { return merge_key16_on() && d.mg_G > 0 && !(d.mg_two && d.mg_G > 4); }
 constexpr int kTileShift = 11;           // log2(kTileEntries)
 constexpr int kTileColBits = 20;         // column offset bits of a packed sorted-tile entry
 // Offsets >= kTileDiagMark mark a diagonal entry: offset - kTileDiagMark = its row in the block (so
@@ -338,13 +371,20 @@ inline void with_tile_kind(const DevCSR &A, F f)
 }
 // f(std::integral_constant<int, G>, std::bool_constant<LDSACC>) with the group size (4 or 8) and the
 // accumulator placement (DevCSR::mg_acc) of A's merged row groups; false, f not called, if A has none
+// ... and std::bool_constant<K16>: narrow keys (DevCSR::mg_k16)
 template <class F>
 inline bool with_merged_kind(const DevCSR &A, F f)
 {
-    if (A.mg_G == 8 && A.mg_acc) f(std::integral_constant<int, 8>{}, std::true_type{});
-    else if (A.mg_G == 8) f(std::integral_constant<int, 8>{}, std::false_type{});
-    else if (A.mg_G == 4 && A.mg_acc) f(std::integral_constant<int, 4>{}, std::true_type{});
-    else if (A.mg_G == 4) f(std::integral_constant<int, 4>{}, std::false_type{});
+    auto acc = [&](auto G, auto K16) {
+        if (A.mg_acc) f(G, std::true_type{}, K16);
+        else f(G, std::false_type{}, K16);
+    };
+    auto keys = [&](auto G) {
+        if (A.mg_k16) acc(G, std::true_type{});
+        else acc(G, std::false_type{});
+    };
+    if (A.mg_G == 8) keys(std::integral_constant<int, 8>{});
+    else if (A.mg_G == 4) keys(std::integral_constant<int, 4>{});
     else return false;
     return true;
 }

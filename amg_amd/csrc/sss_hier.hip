@@ -1525,6 +1525,42 @@ extern "C" int sss_hip_level_info_get(sss_hip_hier *h, int level, sss_hip_level_
     return 0;
 }
 
+// which: 0 the level matrix, 1 / 2 the F / C class's [N | L] copy, 3 / 4 its L copy
+static const DevCSR *merged_copy(sss_hip_hier *h, int level, int which)
+{
+    if (!h || level < 0 || level >= h->nl || which < 0 || which > 4) return nullptr;
+    auto &L = h->L[level];
+    if (which == 0) return &L.A;
+    const auto &p = L.sm.pass[(which - 1) & 1];
+    return which <= 2 ? &p.ts_nl : &p.ts_lo;
+}
+
+extern "C" int sss_hip_merged_key_stats(sss_hip_hier *h, int level, int which, long long *out)
+{
+    const DevCSR *M = merged_copy(h, level, which);
+    if (!M || !out) return ERROR_INPUT_PAR;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!M->mg_k16) return 1;   // no merged copy, or one with 32-bit keys
+    for (int i = 0; i < 5; ++i) out[i] = M->mg_cnt[i];
+    out[5] = M->nnz, out[6] = M->mg_nd, out[7] = M->mg_ne;
+    return 0;
+}
+
+extern "C" int sss_hip_merged_keys_get(sss_hip_hier *h, int level, int which, unsigned short *k16, int *desc,
+                                       unsigned *esc)
+{
+    const DevCSR *M = merged_copy(h, level, which);
+    if (!M || !M->mg_k16 || !k16 || !desc) return ERROR_INPUT_PAR;
+    SSS_HIP(hipDeviceSynchronize());
+    SSS_HIP(hipMemcpy(k16, M->mg_k16, sizeof(unsigned short) * (size_t)M->nnz, hipMemcpyDeviceToHost));
+    SSS_HIP(hipMemcpy(desc, M->mg_d, sizeof(int4) * (size_t)M->mg_nd, hipMemcpyDeviceToHost));
+    if (M->mg_ne > 0) {
+        if (!esc) return ERROR_INPUT_PAR;
+        SSS_HIP(hipMemcpy(esc, M->mg_ke, sizeof(unsigned) * (size_t)M->mg_ne, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 // Per-level time of the cycle: level_ms[l] = level l's steps (pre-smoothing, residual, restriction,
 // zero fill; prolongation, post-smoothing; the coarsest level: its solve; a single-workgroup tail:
 // at its first level), averaged over reps eager cycles with an event between the steps (launch gaps

@@ -881,7 +881,8 @@ __global__ __launch_bounds__(kBlock) void relax_range_wave(int lo, int hi, const
 // Stage 0 over the reordered pass rows [N_i | L_i] (local row q = global lo + q):
 //   P_q = b - sum_{N_i} a x;  y_q = (P_q - sum_{L_i} a x) / d   (x from before the pass)
 // (LDSACC: merged groups with the lanes' accumulators in LDS, DevCSR::mg_acc)
-template <int PATH, bool LDSACC = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
+// (K16: narrow keys, DevCSR::mg_k16)
+template <int PATH, bool LDSACC = false, bool K16 = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
 __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int *__restrict__ split,
                                                     const double *__restrict__ b, XSrc x,
                                                     const double *__restrict__ deff, double *__restrict__ P,
@@ -925,8 +926,9 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
         __shared__ double acc[LDSACC ? 4 * 2 * G * kMergeAccDoubles : 1];
         int g = 0, u = 0;
         double n_sum = 0.0, l_sum = 0.0;
-        if (merged_block<G, 2, LDSACC>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, [&](int c) -> double { return x(c); },
-                                       red, acc, g, u, n_sum, l_sum)) {
+        constexpr bool K = K16 && 2 * G <= 8;   // (three accumulator bits; G = 8 is never uploaded narrow)
+        if (merged_block<G, 2, LDSACC, K>(M.mg_gp, M.mg_ng, M.mg_W, merged_keys_of(M), M.mg_v,
+                                          [&](int c) -> double { return x(c); }, red, acc, g, u, n_sum, l_sum)) {
             const int q = g * G + u;
             if (q < M.n) {
                 const double Pq = b[lo + q] - n_sum;
@@ -1015,7 +1017,7 @@ __global__ __launch_bounds__(kBlock) void ts_stage0(int lo, DevCSR M, const int 
 
 // Inner step over the L-only rows:  y_q = (P_q - sum_{L_i} a yp[j - lo]) / d  (keeps yp_q if |d| small)
 // (column c reads ycols[c - col_off]; a row with |d| small keeps ykeep[q]; rows are lo + q)
-template <int PATH, bool LDSACC = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
+template <int PATH, bool LDSACC = false, bool K16 = false>   // 0 tile, 1 wave chain, 2 wave tree (free order)
 __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const double *__restrict__ deff,
                                                    const double *__restrict__ P, const double *ycols, int col_off,
                                                    const double *ykeep, double *__restrict__ y)
@@ -1054,8 +1056,8 @@ __global__ __launch_bounds__(kBlock) void ts_inner(int lo, DevCSR M, const doubl
         __shared__ double acc[LDSACC ? 4 * G * kMergeAccDoubles : 1];
         int g = 0, u = 0;
         double l_sum = 0.0, unused = 0.0;
-        if (merged_block<G, 1, LDSACC>(M.mg_gp, M.mg_ng, M.mg_W, M.mg_k, M.mg_v, fetch, red, acc, g, u, l_sum,
-                                       unused)) {
+        if (merged_block<G, 1, LDSACC, K16>(M.mg_gp, M.mg_ng, M.mg_W, merged_keys_of(M), M.mg_v, fetch, red, acc, g, u,
+                                            l_sum, unused)) {
             const int q = g * G + u;
             if (q < M.n) finish(q, P[q] - l_sum);
         }
@@ -1124,9 +1126,9 @@ void launch_ts_stage0(const DevCSR &M, int lo, const int *split, const double *b
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + x gathers, b, deff, P and y
-    if (M.mg_two && with_merged_kind(M, [&](auto G, auto ACC) {
-            hipLaunchKernelGGL((ts_stage0<decltype(G)::value, decltype(ACC)::value>), dim3(M.ngrid), dim3(kBlock), 0, s,
-                               lo, M, split, b, x, deff, P, y);
+    if (M.mg_two && with_merged_kind(M, [&](auto G, auto ACC, auto K16) {
+            hipLaunchKernelGGL((ts_stage0<decltype(G)::value, decltype(ACC)::value, decltype(K16)::value>), dim3(M.ngrid),
+                               dim3(kBlock), 0, s, lo, M, split, b, x, deff, P, y);
         }))
         return;
     if (M.vec_rows)
@@ -1148,9 +1150,9 @@ void launch_ts_inner(const DevCSR &M, int lo, const double *deff, const double *
 {
     if (M.n == 0) return;
     ledger_add((double)M.stream_bytes + 40.0 * M.n);   // + y gathers, deff, P, ykeep and y
-    if (with_merged_kind(M, [&](auto G, auto ACC) {
-            hipLaunchKernelGGL((ts_inner<decltype(G)::value, decltype(ACC)::value>), dim3(M.ngrid), dim3(kBlock), 0, s,
-                               lo, M, deff, P, ycols, col_off, ykeep, y);
+    if (with_merged_kind(M, [&](auto G, auto ACC, auto K16) {
+            hipLaunchKernelGGL((ts_inner<decltype(G)::value, decltype(ACC)::value, decltype(K16)::value>), dim3(M.ngrid),
+                               dim3(kBlock), 0, s, lo, M, deff, P, ycols, col_off, ykeep, y);
         }))
         return;
     if (M.vec_rows)

@@ -481,6 +481,122 @@ static void build_merged(const SSS_MAT &h, const int *seg, int G, std::vector<in
     gp[ng] = rp[n];
 }
 
+// SSS_HIP_MERGE_KEY16 (read per upload: tests compare both ways)
+bool merge_key16_on()
+{
+    // 0: 32-bit keys.  Default 1, measured on 7-pt 400^3 against the previous commit's library, four
+    // runs each alternating in one job (profiles/merged_key16/): 18.27-18.34 -> 17.90-18.00 ms per step
+    const char *e = getenv("SSS_HIP_MERGE_KEY16");
+    return !(e && *e == '0');
+}
+
+// Narrow keys of a merged copy (DevCSR::mg_k16 / mg_d / mg_ke).  Within a group the entries are
+// sorted by column, so the 64 columns of a chunk lie close together, but for the chunk that crosses
+// from a row's F-range columns to its C-range columns.  Per chunk: `split` is the first lane after
+// the widest column gap (the lowest such lane on ties); one base if last - first < 2^13, else two
+// bases cut at `split` if both halves span < 2^13, else the chunk is wide and its whole share (one
+// wave's entries: the kernels branch once per wave, not per chunk) keeps 32-bit keys.
+void merged_narrow(const unsigned *keys, long long nnz, const int *gp, int ng, bool two, int W, unsigned short *k16,
+                   int *desc, std::vector<unsigned> &esc, long long cnt[5])
+{
+    constexpr int kSpan = 1 << kMergeDeltaBits;
+    const long long nd = merged_desc_slots(nnz, ng, W);
+    std::memset(desc, 0, sizeof(int) * 4 * (size_t)nd);
+    std::vector<long long> eoff((size_t)ng * W + 1, 0);   // per share: its escaped keys (then their first position)
+    std::mutex mu;
+    for (int i = 0; i < 5; ++i) cnt[i] = 0;
+    auto acc_of = [two](unsigned q) { return two ? ((q >> 1) & 4u) | (q & 3u) : q & 7u; };
+    parallel_chunks(ng, 64, [&](int glo, int ghi) {
+        long long c[5] = {};
+        for (int g = glo; g < ghi; ++g) {
+            const long long k0 = gp[g], len = gp[g + 1] - k0, per = (len + W - 1) / W;
+            for (int part = 0; part < W; ++part) {
+                const long long a = k0 + std::min(len, part * per), e = k0 + std::min(len, (part + 1) * per);
+                if (a >= e) continue;
+                const long long d0 = (a >> 6) + (long long)g * W + part;
+                bool wide = false;
+                for (long long kb = a, ch = 0; kb < e; kb += 64, ++ch) {
+                    const int m = (int)std::min<long long>(64, e - kb);
+                    int *d = desc + 4 * (d0 + ch);
+                    const int first = (int)(keys[kb] >> kMergeShift), last = (int)(keys[kb + m - 1] >> kMergeShift);
+                    int split = 64, gap = 0;
+                    for (int l = 1; l < m; ++l) {
+                        const int w = (int)(keys[kb + l] >> kMergeShift) - (int)(keys[kb + l - 1] >> kMergeShift);
+                        if (w > gap) gap = w, split = l;
+                    }
+                    ++c[0];
+                    int lo = first, hi = first, kind;
+                    if (last - first < kSpan) {
+                        kind = 1, split = 64;
+                    } else {
+                        hi = (int)(keys[kb + split] >> kMergeShift);
+                        const int below = (int)(keys[kb + split - 1] >> kMergeShift) - first;
+                        kind = (below < kSpan && last - hi < kSpan) ? 2 : 3;
+                    }
+                    ++c[kind];
+                    if (kind == 3) {   // no narrow form: zero keys, the share escapes
+                        wide = true;
+                        d[0] = d[1] = 0, d[2] = 64, d[3] = -1;
+                        for (int l = 0; l < m; ++l) k16[kb + l] = 0;
+                        continue;
+                    }
+                    d[0] = lo, d[1] = hi, d[2] = split, d[3] = -1;
+                    for (int l = 0; l < m; ++l) {
+                        const unsigned q = keys[kb + l];
+                        const unsigned delta = (q >> kMergeShift) - (unsigned)(l < split ? lo : hi);
+                        k16[kb + l] = (unsigned short)(delta << 3 | acc_of(q));
+                    }
+                }
+                if (wide) {
+                    eoff[(size_t)g * W + part] = e - a;
+                    c[4] += (e - a + 63) >> 6;
+                }
+            }
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        for (int i = 0; i < 5; ++i) cnt[i] += c[i];
+    });
+    long long run = 0;
+    for (auto &x : eoff) {
+        const long long l = x;
+        x = run, run += l;
+    }
+    esc.resize((size_t)run);
+    parallel_chunks(ng, 64, [&](int glo, int ghi) {
+        for (int g = glo; g < ghi; ++g) {
+            const long long k0 = gp[g], len = gp[g + 1] - k0, per = (len + W - 1) / W;
+            for (int part = 0; part < W; ++part) {
+                const size_t s = (size_t)g * W + part;
+                if (eoff[s + 1] == eoff[s]) continue;
+                const long long a = k0 + std::min(len, part * per), e = k0 + std::min(len, (part + 1) * per);
+                const long long d0 = (a >> 6) + (long long)g * W + part;
+                std::memcpy(esc.data() + eoff[s], keys + a, sizeof(unsigned) * (size_t)(e - a));
+                for (long long kb = a, ch = 0; kb < e; kb += 64, ++ch) desc[4 * (d0 + ch) + 3] = (int)(eoff[s] + 64 * ch);
+            }
+        }
+    });
+}
+
+// (tests: the narrowing without a GPU.  esc holds up to esc_cap keys -- nnz always suffices;
+// *n_esc receives the count; desc: merged_desc_slots x 4 ints, *n_desc the slots)
+extern "C" int sss_hip_merged_narrow(const unsigned *keys, long long nnz, const int *gp, int ng, int two, int W,
+                                     unsigned short *k16, int *desc, long long desc_cap, long long *n_desc,
+                                     unsigned *esc, long long esc_cap, long long *n_esc, long long *counts)
+{
+    if (!keys || !gp || ng < 0 || nnz < 0 || (W != 1 && W != 2 && W != 4) || !k16 || !desc || !n_desc || !n_esc || !counts)
+        return ERROR_INPUT_PAR;
+    if (nnz >= (1ll << 31) || gp[ng] != nnz) return ERROR_INPUT_PAR;
+    const long long nd = merged_desc_slots(nnz, ng, W);
+    *n_desc = nd;
+    if (desc_cap < nd) return ERROR_INPUT_PAR;
+    std::vector<unsigned> e;
+    merged_narrow(keys, nnz, gp, ng, two != 0, W, k16, desc, e, counts);
+    *n_esc = (long long)e.size();
+    if ((long long)e.size() > esc_cap || (!e.empty() && !esc)) return ERROR_INPUT_PAR;
+    if (!e.empty()) std::memcpy(esc, e.data(), sizeof(unsigned) * e.size());
+    return 0;
+}
+
 DevDict devdict(const DevCSR &A, int blo)
 {
     DevDict t;
@@ -838,6 +954,29 @@ static int merge_acc(int G, bool two)
     return 1;
 }
 
+// d's merged copy (mg_G, mg_ng, mg_W, mg_two set) with narrow keys from its sorted 32-bit keys and
+// group bounds on the host
+static int merged_upload_narrow(DevCSR &d, const unsigned *hk, const int *hgp)
+{
+    const long long nd = merged_desc_slots(d.nnz, d.mg_ng, d.mg_W);
+    HostBuf<unsigned short> k16;
+    HostBuf<int> desc;
+    std::vector<unsigned> esc;
+    k16.resize((size_t)d.nnz);
+    desc.resize(4 * (size_t)nd);
+    merged_narrow(hk, d.nnz, hgp, d.mg_ng, d.mg_two, d.mg_W, k16.data(), desc.data(), esc, d.mg_cnt);
+    d.mg_nd = nd, d.mg_ne = (long long)esc.size();
+    d.mg_k16 = dev_alloc<unsigned short>((size_t)d.nnz);
+    d.mg_d = dev_alloc<int4>((size_t)nd);
+    d.mg_ke = dev_alloc<unsigned>(std::max<size_t>(esc.size(), 1));
+    if (!d.mg_k16 || !d.mg_d || !d.mg_ke) return hip_fail(hipErrorOutOfMemory, "hipMalloc(merged)", __FILE__, __LINE__);
+    if (int rc = h2d(d.mg_k16, k16.data(), sizeof(unsigned short) * (size_t)d.nnz)) return rc;
+    if (int rc = h2d(d.mg_d, desc.data(), sizeof(int4) * (size_t)nd)) return rc;
+    if (!esc.empty())
+        if (int rc = h2d(d.mg_ke, esc.data(), sizeof(unsigned) * esc.size())) return rc;
+    return 0;
+}
+
 int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *seg)
 {
     PhaseTimer pt("devcsr");
@@ -908,12 +1047,18 @@ int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *se
         d.mg_W = d.mg_W >= 4 ? 4 : d.mg_W >= 2 ? 2 : 1;
         d.mg_acc = merge_acc(d.mg_G, d.mg_two);
         d.ngrid = (d.mg_ng + 4 / d.mg_W - 1) / (4 / d.mg_W);
+        const bool narrow = merged_key16_ok(d);
         d.mg_gp = dev_alloc<int>(gp.size());
-        d.mg_k = dev_alloc<unsigned>(mk.size());
+        if (!narrow) d.mg_k = dev_alloc<unsigned>(mk.size());
         d.mg_v = dev_alloc<double>(mv.size());
-        if (!d.mg_gp || !d.mg_k || !d.mg_v) return hip_fail(hipErrorOutOfMemory, "hipMalloc(merged)", __FILE__, __LINE__);
+        if (!d.mg_gp || (!narrow && !d.mg_k) || !d.mg_v)
+            return hip_fail(hipErrorOutOfMemory, "hipMalloc(merged)", __FILE__, __LINE__);
         if (int rc = h2d(d.mg_gp, gp.data(), sizeof(int) * gp.size())) return rc;
-        if (int rc = h2d(d.mg_k, mk.data(), sizeof(unsigned) * mk.size())) return rc;
+        if (narrow) {
+            if (int rc = merged_upload_narrow(d, mk.data(), gp.data())) return rc;
+        } else if (int rc = h2d(d.mg_k, mk.data(), sizeof(unsigned) * mk.size())) {
+            return rc;
+        }
         if (int rc = h2d(d.mg_v, mv.data(), sizeof(double) * mv.size())) return rc;
     }
     if (d.vec_rows && !((enc & kEncMergedOnly) && d.mg_G > 0) && device_builders_on() && d.nnz > 0)
@@ -1076,6 +1221,8 @@ int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split, int enc, const int *se
     } else {
         d.stream_bytes = 12 * nnz + 4 * (rows + 1) + 8 * (nb + 1);
     }
+    // narrow merged keys: 2 B per entry, the descriptors and the escaped shares' 32-bit keys
+    if (d.mg_k16) d.stream_bytes += 2 * nnz + 16 * d.mg_nd + 4 * d.mg_ne - 4 * nnz;
     return 0;
 }
 
@@ -1105,6 +1252,9 @@ void devcsr_free(DevCSR &d)
     dev_free(d.mg_gp);
     dev_free(d.mg_k);
     dev_free(d.mg_v);
+    dev_free(d.mg_k16);
+    dev_free(d.mg_d);
+    dev_free(d.mg_ke);
     dev_free(d.dv_code);
     dev_free(d.dv_ell);
     dev_free(d.dv_ell_base);
@@ -1252,9 +1402,10 @@ __global__ __launch_bounds__(kBlock) void spmv_wave(int n, const int *__restrict
 
 // Free order, merged row groups (DevCSR::mg_*): W waves per group of G rows (merged_block).
 // (LDSACC: the lanes' accumulators in LDS, DevCSR::mg_acc)
-template <int OP, bool NORM, int G, bool LDSACC = false>
+// (K16: narrow keys, DevCSR::mg_k16)
+template <int OP, bool NORM, int G, bool LDSACC = false, bool K16 = false>
 __global__ __launch_bounds__(kBlock) void spmv_merged(int n, int ng, int W, const int *__restrict__ gp,
-                                                      const unsigned *__restrict__ mk, const double *__restrict__ mv,
+                                                      MergedKeys mk, const double *__restrict__ mv,
                                                       const double *__restrict__ x, const double *__restrict__ b,
                                                       double *__restrict__ y, double alpha, int cap,
                                                       double *__restrict__ partial)
@@ -1264,8 +1415,8 @@ __global__ __launch_bounds__(kBlock) void spmv_merged(int n, int ng, int W, cons
     __shared__ double acc[LDSACC ? 4 * G * kMergeAccDoubles : 1];
     int g = 0, u = 0;
     double sr = 0.0, unused = 0.0, sq = 0.0;
-    if (merged_block<G, 1, LDSACC>(gp, ng, W, mk, mv, [&](int c) -> double { return x[c]; }, red, acc, g, u, sr,
-                                   unused)) {
+    if (merged_block<G, 1, LDSACC, K16>(gp, ng, W, mk, mv, [&](int c) -> double { return x[c]; }, red, acc, g, u, sr,
+                                        unused)) {
         const int r = g * G + u;
         if (r < n) sq = spmv_row_out<OP, NORM>(r, sr, alpha, b, y, cap);
     }
@@ -1279,10 +1430,10 @@ template <int OP, bool NORM>
 static void launch_op(const DevCSR &A, double alpha, const double *x, const double *b, double *y, int cap,
                       double *partial, hipStream_t s)
 {
-    if (with_merged_kind(A, [&](auto G, auto ACC) {
-            hipLaunchKernelGGL((spmv_merged<OP, NORM, decltype(G)::value, decltype(ACC)::value>), dim3(A.ngrid),
-                               dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W, A.mg_gp, A.mg_k, A.mg_v, x, b, y, alpha, cap,
-                               partial);
+    if (with_merged_kind(A, [&](auto G, auto ACC, auto K16) {
+            hipLaunchKernelGGL((spmv_merged<OP, NORM, decltype(G)::value, decltype(ACC)::value, decltype(K16)::value>),
+                               dim3(A.ngrid), dim3(kBlock), 0, s, A.n, A.mg_ng, A.mg_W, A.mg_gp, merged_keys_of(A), A.mg_v,
+                               x, b, y, alpha, cap, partial);
         }))
         return;
     if (A.vec_rows)

@@ -954,32 +954,67 @@ __device__ __forceinline__ double wave_row_sum(int k0, int k1, const int *__rest
 
 // (U, the loads in flight per lane, changes no sum: each lane still adds its entries in increasing
 // position into the same accumulators)
-template <int G, int S, class Fetch>
-__device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__restrict__ mk,
+
+// The chunk descriptors of a narrow copy are read through the constant address space: nothing
+// writes them while a kernel runs, the index is the same in every lane, and loads from this space
+// at a uniform address are scalar loads whatever stores the kernel has issued before.
+typedef const int __attribute__((address_space(4))) *MergedDesc;   // four ints per chunk
+__device__ __forceinline__ MergedDesc merged_desc(const int4 *d) { return (MergedDesc)(unsigned long long)d; }
+struct MergedChunk {
+    int lo, hi, split;
+};
+__device__ __forceinline__ MergedChunk merged_chunk(MergedDesc d, int c)
+{
+    return MergedChunk{d[4 * c], d[4 * c + 1], d[4 * c + 2]};
+}
+// Narrow keys (DevCSR::mg_k16, KT = unsigned short): the one decode of every merged kernel.  q: the
+// entry's 16-bit key, d: its chunk's descriptor (the same in every lane: scalar registers), el: the
+// entry's lane in its chunk (its position from the share's start, mod 64).
+__device__ __forceinline__ int merged_col16(unsigned q, const MergedChunk &d, int el)
+{
+    return (int)(q >> 3) + (el < d.split ? d.lo : d.hi);
+}
+// the register form's accumulator code (segment << 3 | row) of a key of either width
+template <int S, class KT>
+__device__ __forceinline__ unsigned merged_code(unsigned q)
+{
+    if constexpr (sizeof(KT) == 2) return S == 2 ? ((q & 4u) << 1) | (q & 3u) : q & 7u;
+    else return q & ((1u << kMergeShift) - 1);
+}
+// md (narrow keys only): the descriptor of the chunk at k0, the start of the wave's share
+template <int G, int S, class KT, class Fetch>
+__device__ __forceinline__ void merged_sums(int k0, int k1, const KT *__restrict__ mk, MergedDesc md,
                                             const double *__restrict__ mv, Fetch fetch, double (&s0)[G],
                                             double (&s1)[G])
 {
     constexpr int U = 8;
+    constexpr bool K16 = sizeof(KT) == 2;
     const int lane = threadIdx.x & 63;
+    const int lastc = ((k1 - k0 + 63) >> 6) - 1, lastl = (k1 - 1 - k0) & 63;   // the share's last chunk, last lane
 #pragma unroll
     for (int u = 0; u < G; ++u) s0[u] = 0.0, s1[u] = 0.0;
     // two segments (the two-stage split copies, ts_stage0): the product formed where the entry is
     // added.  Measured at 400^3 (levels 5-6, the longest groups) 8-10 % faster than the form below,
     // which holds every gather in flight at once (86 VGPRs against 64: 5 waves per SIMD)
-    for (int k = k0 + lane; k < k1 && S == 2; k += 64 * U) {
+    for (int k = k0 + lane, cb = 0; k < k1 && S == 2; k += 64 * U, cb += U) {
         unsigned q[U];
         double a[U];
+        MergedChunk d[U];
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             const int kk = k + 64 * t;
             q[t] = kk < k1 ? mk[kk] : 0u;
             a[t] = kk < k1 ? mv[kk] : 0.0;
+            if constexpr (K16) d[t] = merged_chunk(md, min(cb + t, lastc));
         }
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             if (k + 64 * t >= k1) break;
-            const double p = a[t] * fetch((int)(q[t] >> kMergeShift));
-            const unsigned key = q[t] & ((1u << kMergeShift) - 1);
+            int col;
+            if constexpr (K16) col = merged_col16(q[t], d[t], lane);
+            else col = (int)(q[t] >> kMergeShift);
+            const double p = a[t] * fetch(col);
+            const unsigned key = merged_code<S, KT>(q[t]);
 #pragma unroll
             for (int u = 0; u < G; ++u) {
                 s0[u] += key == (unsigned)u ? p : 0.0;
@@ -987,9 +1022,10 @@ __device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__re
             }
         }
     }
-    for (int k = k0 + lane; k < k1 && S == 1; k += 64 * U) {
+    for (int k = k0 + lane, cb = 0; k < k1 && S == 1; k += 64 * U, cb += U) {
         unsigned q[U];
         double a[U], xv[U];
+        MergedChunk d[U];
         // keys and values loaded unconditionally (clamped into the group), every x gather issued
         // before any product is formed: with the multiply under each gather's condition the
         // compiler waited for each gather in turn.  An entry past the group adds +0.0 to row 0's
@@ -1000,14 +1036,20 @@ __device__ __forceinline__ void merged_sums(int k0, int k1, const unsigned *__re
             const int kk = k + 64 * t, kc = kk < k1 ? kk : k1 - 1;
             q[t] = mk[kc];
             a[t] = mv[kc];
+            if constexpr (K16) d[t] = merged_chunk(md, min(cb + t, lastc));   // (kc's chunk)
         }
 #pragma unroll
-        for (int t = 0; t < U; ++t) xv[t] = k + 64 * t < k1 ? fetch((int)(q[t] >> kMergeShift)) : 0.0;
+        for (int t = 0; t < U; ++t) {
+            int col;
+            if constexpr (K16) col = merged_col16(q[t], d[t], k + 64 * t < k1 ? lane : lastl);   // (kc's lane)
+            else col = (int)(q[t] >> kMergeShift);
+            xv[t] = k + 64 * t < k1 ? fetch(col) : 0.0;
+        }
 #pragma unroll
         for (int t = 0; t < U; ++t) {
             const bool live = k + 64 * t < k1;
             const double p = live ? a[t] * xv[t] : 0.0;
-            const unsigned key = live ? q[t] & ((1u << kMergeShift) - 1) : 0u;
+            const unsigned key = live ? merged_code<S, KT>(q[t]) : 0u;
 #pragma unroll
             for (int u = 0; u < G; ++u) {
                 s0[u] += key == (unsigned)u ? p : 0.0;
@@ -1053,54 +1095,73 @@ constexpr int kMergeLdsChunks = S == 2 ? 6 : 8;   // chunks per batch (U changes
 template <int G, int S>
 constexpr unsigned kMergeKeyMask = S == 2 ? (8u | (unsigned)(G - 1)) : (unsigned)(G - 1);
 // (accumulator a = segment * G + row  ->  its key)
-template <int G, int S>
+// DENSE (the kernels of a copy with narrow keys, whose 16-bit keys hold segment << 2 | row): the
+// accumulator of (segment, row) at slot segment * G + row of its wave's S * G instead -- the same
+// accumulators under other addresses, so that a narrow key's low bits are its slot.
+template <int G, int S, bool DENSE = false>
 __device__ __forceinline__ constexpr int merged_acc_key(int a)
 {
-    return S == 2 ? (a / G) << 3 | (a % G) : a;
+    return S == 2 && !DENSE ? (a / G) << 3 | (a % G) : a;
 }
 // first double of wave w's accumulators in a block's 4 * S * G * kMergeAccDoubles
-template <int G, int S>
+template <int G, int S, bool DENSE = false>
 __device__ __forceinline__ int merged_acc_base(int w)
 {
-    if (S == 2 && G == 4) return ((w >> 1) * 16 + (w & 1) * 4) * kMergeAccDoubles;
+    if (S == 2 && G == 4 && !DENSE) return ((w >> 1) * 16 + (w & 1) * 4) * kMergeAccDoubles;
     return w * (S * G * kMergeAccDoubles);
 }
-template <int G, int S, int C, class Fetch>
-__device__ __forceinline__ void merged_batch_lds(const unsigned *__restrict__ pk, const double *__restrict__ pv,
-                                                 int last_n, Fetch fetch, double *mine)
+// the LDS slot of an entry's key (32-bit keys in a DENSE kernel: a share that kept them)
+template <int G, int S, bool DENSE, class KT>
+__device__ __forceinline__ unsigned merged_slot(unsigned q)
 {
+    static_assert(kMergeKeyMask<G, S> < (1u << kMergeShift), "key bits");
+    static_assert(!DENSE || S * G <= 8, "accumulator bits of a narrow key");
+    if constexpr (sizeof(KT) == 2) return q & (unsigned)(S * G - 1);
+    else if constexpr (DENSE && S == 2) return ((q >> 1) & (unsigned)G) | (q & (unsigned)(G - 1));
+    else return q & kMergeKeyMask<G, S>;
+}
+// pd (narrow keys): the descriptors of the batch's chunks
+template <int G, int S, int C, bool DENSE, class KT, class Fetch>
+__device__ __forceinline__ void merged_batch_lds(const KT *__restrict__ pk, MergedDesc pd,
+                                                 const double *__restrict__ pv, int last_n, Fetch fetch, double *mine)
+{
+    constexpr bool K16 = sizeof(KT) == 2;
     const int lane = threadIdx.x & 63;
     const int ll = min(lane, last_n - 1);   // the last chunk holds last_n (1 ... 64) entries
     unsigned q[C];
     double a[C], xv[C];
+    MergedChunk d[C];
 #pragma unroll
     for (int t = 0; t < C; ++t) {
         const int o = 64 * t + (t == C - 1 ? ll : lane);
         q[t] = pk[o];
         a[t] = pv[o];
+        if constexpr (K16) d[t] = merged_chunk(pd, t);
     }
 #pragma unroll
-    for (int t = 0; t < C; ++t) xv[t] = fetch((int)(q[t] >> kMergeShift));
+    for (int t = 0; t < C; ++t) {
+        if constexpr (K16) xv[t] = fetch(merged_col16(q[t], d[t], t == C - 1 ? ll : lane));
+        else xv[t] = fetch((int)(q[t] >> kMergeShift));
+    }
 #pragma unroll
     for (int t = 0; t < C; ++t) {
-        static_assert(kMergeKeyMask<G, S> < (1u << kMergeShift), "key bits");
-        const unsigned key = q[t] & kMergeKeyMask<G, S>;
+        const unsigned key = merged_slot<G, S, DENSE, KT>(q[t]);
         double p = a[t] * xv[t];
         if (t == C - 1) p = lane < last_n ? p : 0.0;
         atomicAdd(&mine[key * kMergeAccDoubles], p);   // ds_add_f64, no return value
     }
 }
 // (nch is the same in every lane: a chain of scalar branches)
-template <int G, int S, int C, class Fetch>
-__device__ __forceinline__ void merged_batch_dispatch(int nch, const unsigned *__restrict__ pk,
+template <int G, int S, int C, bool DENSE, class KT, class Fetch>
+__device__ __forceinline__ void merged_batch_dispatch(int nch, const KT *__restrict__ pk, MergedDesc pd,
                                                       const double *__restrict__ pv, int last_n, Fetch fetch,
                                                       double *mine)
 {
     if constexpr (C == 1) {
-        merged_batch_lds<G, S, 1>(pk, pv, last_n, fetch, mine);
+        merged_batch_lds<G, S, 1, DENSE>(pk, pd, pv, last_n, fetch, mine);
     } else {
-        if (nch == C) merged_batch_lds<G, S, C>(pk, pv, last_n, fetch, mine);
-        else merged_batch_dispatch<G, S, C - 1>(nch, pk, pv, last_n, fetch, mine);
+        if (nch == C) merged_batch_lds<G, S, C, DENSE>(pk, pd, pv, last_n, fetch, mine);
+        else merged_batch_dispatch<G, S, C - 1, DENSE>(nch, pk, pd, pv, last_n, fetch, mine);
     }
 }
 // The xor-butterfly's sums, as its lane 0 holds them, of the wave's S * G accumulators, taken out
@@ -1111,13 +1172,13 @@ __device__ __forceinline__ void merged_batch_dispatch(int nch, const unsigned *_
 // pairs with i + LP (m + off / LP)) and the steps LP / 2 ... 1 across the LP lanes.  Every step
 // adds the butterfly's pairs, the lower element on the left as there, so the sums keep their bits.
 // out[a] = the sum of accumulator a (written by lane a * LP).
-template <int G, int S>
+template <int G, int S, bool DENSE = false>
 __device__ __forceinline__ void merged_tree_lds(const double *acc, double *out)
 {
     constexpr int NA = S * G, LP = 64 / NA;
     static_assert(NA >= 2 && NA <= 32 && LP * NA == 64, "accumulators per wave");
     const int lane = threadIdx.x & 63, a = lane / LP, i = lane % LP;
-    const double *col = acc + merged_acc_key<G, S>(a) * kMergeAccDoubles + i;
+    const double *col = acc + merged_acc_key<G, S, DENSE>(a) * kMergeAccDoubles + i;
     wave_sync();   // the other lanes' adds: a wave's LDS operations complete in issue order
     double v[NA];
 #pragma unroll
@@ -1132,8 +1193,9 @@ __device__ __forceinline__ void merged_tree_lds(const double *acc, double *out)
     if (i == 0) out[a] = s;
 }
 // acc: the wave's accumulators; out[segment * G + row] = the wave's sum
-template <int G, int S, class Fetch>
-__device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *__restrict__ mk,
+// md (narrow keys): the descriptor of the chunk at k0, the start of the wave's share
+template <int G, int S, bool DENSE, class KT, class Fetch>
+__device__ __forceinline__ void merged_sums_lds(int k0, int k1, const KT *__restrict__ mk, MergedDesc md,
                                                 const double *__restrict__ mv, Fetch fetch, double *acc,
                                                 double *out)
 {
@@ -1141,16 +1203,16 @@ __device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *
     const int lane = threadIdx.x & 63;
     double *mine = acc + lane;
 #pragma unroll
-    for (int a = 0; a < S * G; ++a) mine[merged_acc_key<G, S>(a) * kMergeAccDoubles] = 0.0;
+    for (int a = 0; a < S * G; ++a) mine[merged_acc_key<G, S, DENSE>(a) * kMergeAccDoubles] = 0.0;
     // (wave-uniform: scalar loop control and base pointers)
     k1 = __builtin_amdgcn_readfirstlane(k1);
-    for (int kb = __builtin_amdgcn_readfirstlane(k0); kb < k1; kb += 64 * U) {
+    for (int kb = __builtin_amdgcn_readfirstlane(k0); kb < k1; kb += 64 * U, md += 4 * U) {
         const int rem = min(k1 - kb, 64 * U), nch = (rem + 63) >> 6, last_n = rem - 64 * (nch - 1);
-        const unsigned *pk = mk + kb;
+        const KT *pk = mk + kb;
         const double *pv = mv + kb;
-        merged_batch_dispatch<G, S, U>(nch, pk, pv, last_n, fetch, mine);
+        merged_batch_dispatch<G, S, U, DENSE>(nch, pk, md, pv, last_n, fetch, mine);
     }
-    merged_tree_lds<G, S>(acc, out);
+    merged_tree_lds<G, S, DENSE>(acc, out);
 }
 
 // Merged groups per 256-thread workgroup: W waves per group (W = 1, 2 or 4, DevCSR::mg_W), so
@@ -1162,24 +1224,41 @@ __device__ __forceinline__ void merged_sums_lds(int k0, int k1, const unsigned *
 // (merged_sums_lds; acc unused otherwise).
 // (W is a power of two: its divisions are shifts; the wave index is a scalar, so the group's bounds
 // are scalar loads)
-template <int G, int S, bool LDSACC, class Fetch>
-__device__ __forceinline__ bool merged_block(const int *__restrict__ gp, int ng, int W, const unsigned *__restrict__ mk,
+// K16: the copy has narrow keys (mk.k16 / mk.d; DevCSR::mg_k16): the wave reads its share's first
+// descriptor and takes the narrow form, or -- esc >= 0, a share with a wide chunk -- the 32-bit form
+// on the share's keys in mk.ke; both with the DENSE accumulator slots.  Without K16 today's kernels.
+template <int G, int S, bool LDSACC, bool K16, class Fetch>
+__device__ __forceinline__ bool merged_block(const int *__restrict__ gp, int ng, int W, const MergedKeys &mk,
                                              const double *__restrict__ mv, Fetch fetch, double *red, double *acc,
                                              int &g_out, int &u_out, double &t0, double &t1)
 {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int wsh = W >= 4 ? 2 : W >= 2 ? 1 : 0, gpb = 4 >> wsh;
     const int g = xcd_bid() * gpb + (w >> wsh), part = w & ((1 << wsh) - 1);
+    int ka = 0, kb = 0;   // the wave's share
+    if (g < ng) {
+        const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + (1 << wsh) - 1) >> wsh;
+        ka = k0 + min(len, part * per), kb = k0 + min(len, (part + 1) * per);
+    }
+    const unsigned *k32 = mk.k;
+    MergedDesc md = nullptr;
+    bool narrow = false;
+    if (K16 && ka < kb) {
+        md = merged_desc(mk.d) + 4 * (long long)__builtin_amdgcn_readfirstlane((ka >> 6) + (g << wsh) + part);
+        const int esc = md[3];
+        narrow = esc < 0;
+        if (!narrow) k32 = mk.ke + ((long long)esc - ka);
+    }
     // the wave's sums: red[(w * 2 + segment) * G + row]
     if (LDSACC && g < ng) {
-        const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + (1 << wsh) - 1) >> wsh;
-        merged_sums_lds<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch,
-                              acc + merged_acc_base<G, S>(w), red + (w * 2) * G);
+        double *mine = acc + merged_acc_base<G, S, K16>(w), *out = red + (w * 2) * G;
+        if (K16 && narrow) merged_sums_lds<G, S, K16>(ka, kb, mk.k16, md, mv, fetch, mine, out);
+        else merged_sums_lds<G, S, K16>(ka, kb, k32, (MergedDesc)nullptr, mv, fetch, mine, out);
     } else {
         double s0[G], s1[G];
         if (g < ng) {
-            const int k0 = gp[g], k1 = gp[g + 1], len = k1 - k0, per = (len + (1 << wsh) - 1) >> wsh;
-            merged_sums<G, S>(k0 + min(len, part * per), k0 + min(len, (part + 1) * per), mk, mv, fetch, s0, s1);
+            if (K16 && narrow) merged_sums<G, S>(ka, kb, mk.k16, md, mv, fetch, s0, s1);
+            else merged_sums<G, S>(ka, kb, k32, (MergedDesc)nullptr, mv, fetch, s0, s1);
         } else {
 #pragma unroll
             for (int u = 0; u < G; ++u) s0[u] = 0.0, s1[u] = 0.0;

@@ -211,6 +211,24 @@ typedef struct sss_hip_level_info {
 } sss_hip_level_info;
 int sss_hip_level_info_get(sss_hip_hier *h, int level, sss_hip_level_info *out);
 int sss_hip_num_levels(sss_hip_hier *h);
+/* Narrow keys of the merged row groups (SSS_HIP_MERGE_KEY16=1): per entry a 16-bit key
+ * (column delta << 3 | accumulator), per chunk of 64 entries of a wave's share a descriptor
+ * {base_lo, base_hi, split, esc} of four ints; a share with a chunk that fits neither one nor two
+ * bases keeps 32-bit keys in an escape list (esc >= 0: the chunk's first key there).
+ * sss_hip_merged_narrow is the host narrowing both builders reproduce: keys are the nnz sorted
+ * 32-bit keys (column << 4 | segment << 3 | row), gp the ng + 1 group bounds, W the waves per group
+ * (1, 2, 4); desc holds desc_cap >= *n_desc slots of four ints, esc up to esc_cap keys (nnz always
+ * suffices); counts[5] = chunks: all, one base, two bases, wide, stored with 32-bit keys.
+ * sss_hip_merged_key_stats: out[8] = those five counts, the entries, descriptor slots and escaped
+ * keys of a level's merged copy (which: 0 the level matrix, 1 / 2 the F / C class's [N | L] copy,
+ * 3 / 4 its L copy); returns 1 (out zeroed) if the copy has no narrow keys.  sss_hip_merged_keys_get
+ * downloads the three arrays of such a copy (sizes as the stats report them). */
+int sss_hip_merged_narrow(const unsigned *keys, long long nnz, const int *gp, int ng, int two, int W,
+                          unsigned short *k16, int *desc, long long desc_cap, long long *n_desc,
+                          unsigned *esc, long long esc_cap, long long *n_esc, long long *counts);
+int sss_hip_merged_key_stats(sss_hip_hier *h, int level, int which, long long *out);
+int sss_hip_merged_keys_get(sss_hip_hier *h, int level, int which, unsigned short *k16, int *desc,
+                            unsigned *esc);
 /* First level of the V-cycle's single-workgroup tail (sss_tail.hip: the small coarse levels,
  * descent, coarsest solve and ascent in one launch), or -1 when the cycle has none. */
 int sss_hip_tail_from(sss_hip_hier *h);
