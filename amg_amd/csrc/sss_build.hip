@@ -5,7 +5,7 @@
 //     key  col << 4 | segment << 3 | row-in-group  (sss_engine.hpp), and
 //   * column-sorted row segments (DevCSR::rows_sorted): each row -- or each of its two segments
 //     [rp, seg) / [seg, rp + 1) -- sorted by column.
-// The host builders (sss_spmv.hip build_merged / sort_row_segments) sort these on the CPU, 3-4 ns
+// The host builders (sss_formats.hip build_merged / sort_row_segments) sort these on the CPU, 3-4 ns
 // per entry on the 16-core box, which was most of the mirror construction left after an
 // overlapped setup (profiles/r03_host_phases_seq_400.txt: 0.5-0.8 s per coarse level).  Here the
 // stored-order CSR already resident in HBM is sorted in place on the GPU by a segmented radix sort.
@@ -170,9 +170,7 @@ int upload_seg(const int *h_seg, int n, int **d_seg)
 {
     *d_seg = nullptr;
     if (!h_seg) return 0;
-    *d_seg = dev_alloc<int>((size_t)n);
-    if (!*d_seg) return hip_fail(hipErrorOutOfMemory, "hipMalloc(seg)", __FILE__, __LINE__);
-    return h2d(*d_seg, h_seg, sizeof(int) * (size_t)n);
+    return dev_upload(*d_seg, h_seg, (size_t)n, "hipMalloc(seg)");
 }
 
 // d.mg_k16 / mg_d / mg_ke from the sorted 32-bit keys (d.mg_gp, mg_ng, mg_W, mg_two set)
@@ -229,12 +227,6 @@ int merged_narrow_device(DevCSR &d, const unsigned *sorted)
 }
 
 }  // namespace
-
-bool device_builders_on()
-{
-    const char *e = getenv("SSS_HIP_GPU_BUILD");   // 0: the host builders (tests compare both)
-    return !(e && *e == '0');
-}
 
 // d: rp / ci / v resident in stored order, d.mg_G > 0.  Fills mg_gp, mg_k, mg_v, mg_ng.
 int merged_build_device(DevCSR &d, const int *h_seg)

@@ -427,14 +427,6 @@ void release(sss_hip_dist *d)
     delete d;
 }
 
-int upload_ints(int **dst, const std::vector<int> &src)
-{
-    *dst = dev_alloc<int>(src.size());
-    if (!*dst) return hip_fail(hipErrorOutOfMemory, "hipMalloc", __FILE__, __LINE__);
-    if (!src.empty()) SSS_HIP(hipMemcpy(*dst, src.data(), sizeof(int) * src.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int sss_hip_rccl_unique_id(unsigned char *id)
@@ -538,7 +530,7 @@ static sss_hip_dist *dist_create_impl(sss_hip_dist *d, PartPlan &plan, const SSS
         if (!tperm.empty()) {
             tinv.resize(nt);
             for (int i = 0; i < nt; ++i) tinv[tperm[i]] = i;
-            if (upload_ints(&d->d_tail_perm, tperm)) return "tail perm";
+            if (dev_upload(d->d_tail_perm, tperm, "hipMalloc")) return "tail perm";
         }
         for (int l = 0; l < d->nagg; ++l) {
             PartLevel &P = plan.L[l];
@@ -594,7 +586,7 @@ static sss_hip_dist *dist_create_impl(sss_hip_dist *d, PartPlan &plan, const SSS
             for (int x : H.scount) H.soff.push_back(H.soff.back() + x);
             H.roff.assign(1, 0);
             for (int x : H.rcount) H.roff.push_back(H.roff.back() + x);
-            if (upload_ints(&H.d_sidx, P.sidx)) return "halo";
+            if (dev_upload(H.d_sidx, P.sidx, "hipMalloc")) return "halo";
             H.d_sbuf = dev_alloc<double>(P.sidx.size());
             if (!H.d_sbuf) return "halo buffer";
         }

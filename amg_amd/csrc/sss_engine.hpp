@@ -82,7 +82,7 @@ struct HostBuf {
     const T &operator[](size_t i) const { return p[i]; }
 };
 
-// Persistent host worker pool for the upload-time data preparation (sss_spmv.hip): the workers
+// Persistent host worker pool for the upload-time data preparation (sss_host.hip): the workers
 // are started once and reused, so a parallel loop costs a wake-up instead of thread creation
 // (h2d alone issued one loop per 32 MiB chunk).  Up to 8 callers' loops at once, idle workers
 // joining any of them; a loop issued from a worker runs inline on it.
@@ -175,8 +175,24 @@ inline void parallel_prefix(int *a, int n)
     });
 }
 
-// Host -> device copy through pinned staging buffers (sss_spmv.hip); returns 0 or an error code.
+// Host -> device copy through pinned staging buffers (sss_host.hip); returns 0 or an error code.
 int h2d(void *dst, const void *src, size_t bytes);
+// dst <- a new device array holding src[0 .. count) (one element for count == 0); `what` names the
+// allocation in the error line.  Returns 0 or an error code; dst is the caller's to free either way.
+template <class T>
+inline int dev_upload(T *&dst, const T *src, size_t count, const char *what, const char *file = __builtin_FILE(),
+                      int line = __builtin_LINE())
+{
+    dst = dev_alloc<T>(count);
+    if (!dst) return hip_fail(hipErrorOutOfMemory, what, file, line);
+    return count > 0 ? h2d(dst, src, sizeof(T) * count) : 0;
+}
+template <class T, class Array>   // ... of a std::vector or HostBuf
+inline int dev_upload(T *&dst, const Array &src, const char *what, const char *file = __builtin_FILE(),
+                      int line = __builtin_LINE())
+{
+    return dev_upload(dst, src.data(), src.size(), what, file, line);
+}
 
 // CSR matrix resident in HBM, plus its CSR-adaptive row blocking for SpMV.
 struct DevCSR {
@@ -290,8 +306,8 @@ constexpr int kMergeShift = 4;           // segment + row-in-group bits of a mer
 constexpr int kMergeDeltaBits = 13;      // column delta bits of a narrow merged key
 // descriptor slots of a narrow merged copy (see DevCSR::mg_d)
 inline long long merged_desc_slots(long long nnz, int ng, int W) { return (nnz >> 6) + (long long)ng * W + 1; }
-// Narrow keys, descriptors and escape list of a sorted 32-bit merged key list (host; both builders'
-// reference, sss_hip_merged_narrow).  k16: nnz, desc: merged_desc_slots() x 4 ints, zero-filled
+// Narrow keys, descriptors and escape list of a sorted 32-bit merged key list (host, sss_formats.hip;
+// both builders' reference, sss_hip_merged_narrow).  k16: nnz, desc: merged_desc_slots() x 4 ints, zero-filled
 // here; esc receives the escaped shares' keys in share order; cnt as DevCSR::mg_cnt.
 void merged_narrow(const unsigned *keys, long long nnz, const int *gp, int ng, bool two, int W, unsigned short *k16,
                    int *desc, std::vector<unsigned> &esc, long long cnt[5]);
@@ -316,6 +332,16 @@ enum { kEncSortedTiles = 1, kEncFreeOrder = 2, kEncDict = 4, kEncMergedOnly = 8,
 // enc: kEnc* flags; seg (kEncFreeOrder only, optional): per row, the absolute CSR position that
 // splits the row into two independently summed segments (two-stage [N_i | L_i] rows).
 int devcsr_upload(DevCSR &d, const SSS_MAT &h, int split = -1, int enc = 0, const int *seg = nullptr);
+// The environment switches an upload reads (SSS_HIP_<name>), as upload_switches() finds them at the
+// time of the call -- per upload, never cached per process.
+struct UploadSwitches {
+    bool dict, ell, ell_base, xell;    // DICT, ELL, ELL_BASE, XELL: "0" turns the format off
+    bool key16, gpu_build;             // MERGE_KEY16, GPU_BUILD
+    int merge_g;                       // MERGE_G as a group size (0, 4 or 8); -1: unset, by row count
+    int merge_min_rows, merge_w, merge_acc;   // MERGE_MIN_ROWS, MERGE_W (1, 2 or 4), MERGE_ACC (0 / 1)
+    int wave_min, free_min;            // WAVE_MIN, FREE_MIN: entries per row
+};
+UploadSwitches upload_switches();
 // encoding flags a hierarchy level uses for its matrices under the options o, and for its
 // transfer operators P_l, R_l
 int level_encoding(const sss_hip_opts &o);

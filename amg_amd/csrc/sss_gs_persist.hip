@@ -748,9 +748,7 @@ int gs_persist_build(PassSchedule &ps, const SSS_MAT &A, int lo, int hi, bool lo
             for (int s0 = ps.h_off[l]; s0 < ps.h_off[l + 1]; s0 += R) ck.push_back(s0);
         ck.push_back(ps.nrows);
         g.nchunks = (int)ck.size() - 1;
-        g.ck = dev_alloc<int>(ck.size());
-        if (!g.ck) return hip_fail(hipErrorOutOfMemory, "hipMalloc(gs chunks)", __FILE__, __LINE__);
-        SSS_HIP(hipMemcpy(g.ck, ck.data(), sizeof(int) * ck.size(), hipMemcpyHostToDevice));
+        if (int rc = dev_upload(g.ck, ck, "hipMalloc(gs chunks)")) return rc;
     }
     int cus = 256;
     {

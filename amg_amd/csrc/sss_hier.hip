@@ -173,8 +173,7 @@ int sss::level_encoding(const sss_hip_opts &o)
         return o.sum_order == 1 ? kEncFreeOrder : 0;
     // dictionary tiles (kEncDict) are offered for the level matrices A_l; uploads of P, R and the
     // two-stage split copies mask them out (their column offsets are not row-relative)
-    const char *dz = getenv("SSS_HIP_DICT");
-    const int dict = (dz && *dz == '0') ? 0 : kEncDict;
+    const int dict = upload_switches().dict ? kEncDict : 0;
     return (o.sorted_tiles ? kEncSortedTiles : 0) | (o.sum_order == 1 ? kEncFreeOrder : 0) | dict | (dict ? kEncXell : 0);
 }
 int sss::level_inner_of(const sss_hip_opts &o, int l, long long rows, long long nnz)
@@ -191,9 +190,8 @@ int sss::transfer_encoding(const sss_hip_opts &o) { return level_encoding(o) & ~
 // block while col - first col repeats; tools/fmt_probe.py reports the formats each operator got).
 int sss::restriction_encoding(const sss_hip_opts &o)
 {
-    const char *bz = getenv("SSS_HIP_ELL_BASE");   // 0: no per-row-based dictionary ELL for R
     int enc = transfer_encoding(o);
-    if ((level_encoding(o) & kEncDict) && !(bz && *bz == '0')) enc |= kEncEllBase;
+    if ((level_encoding(o) & kEncDict) && upload_switches().ell_base) enc |= kEncEllBase;
     return enc;
 }
 

@@ -166,16 +166,10 @@ struct DevMat {
     }
     int up(const SSS_MAT &M)
     {
-        rp = dev_alloc<int>((size_t)M.num_rows + 1);
-        ci = dev_alloc<int>((size_t)std::max(M.num_nnzs, 1));
-        v = dev_alloc<double>((size_t)std::max(M.num_nnzs, 1));
-        if (!rp || !ci || !v) return hip_fail(hipErrorOutOfMemory, "hipMalloc(RAP operand)", __FILE__, __LINE__);
-        if (int rc = h2d(rp, M.row_ptr, sizeof(int) * ((size_t)M.num_rows + 1))) return rc;
-        if (M.num_nnzs > 0) {
-            if (int rc = h2d(ci, M.col_idx, sizeof(int) * (size_t)M.num_nnzs)) return rc;
-            if (int rc = h2d(v, M.val, sizeof(double) * (size_t)M.num_nnzs)) return rc;
-        }
-        return 0;
+        const char *what = "hipMalloc(RAP operand)";
+        if (int rc = dev_upload(rp, M.row_ptr, (size_t)M.num_rows + 1, what)) return rc;
+        if (int rc = dev_upload(ci, M.col_idx, (size_t)M.num_nnzs, what)) return rc;
+        return dev_upload(v, M.val, (size_t)M.num_nnzs, what);
     }
 };
 

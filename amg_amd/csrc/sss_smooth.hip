@@ -30,17 +30,7 @@
 namespace sss {
 
 // ---- host-side planning ---------------------------------------------------------------------
-template <class T>
-static int upload_array(T **dst, const T *src, size_t count)
-{
-    *dst = dev_alloc<T>(count);
-    if (!*dst) return hip_fail(hipErrorOutOfMemory, "hipMalloc(plan array)", __FILE__, __LINE__);
-    return count == 0 ? 0 : h2d(*dst, src, sizeof(T) * count);
-}
-static int upload_ints(int **dst, const std::vector<int> &src) { return upload_array(dst, src.data(), src.size()); }
-static int upload_ints(int **dst, const HostBuf<int> &src) { return upload_array(dst, src.data(), src.size()); }
-static int upload_doubles(double **dst, const HostBuf<double> &src) { return upload_array(dst, src.data(), src.size()); }
-static int upload_doubles(double **dst, const std::vector<double> &src) { return upload_array(dst, src.data(), src.size()); }
+static const char *const kPlanArray = "hipMalloc(plan array)";   // the error line of a failed plan upload
 
 int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind, const DevCSR *dA, int inner,
                    const int *gcls, int enc)
@@ -152,7 +142,7 @@ int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind
         std::vector<int> fill(ps.h_off.begin(), ps.h_off.end()), rows(std::max(ps.nrows, 1));
         for (int i = 0; i < n; ++i)
             if (cls[i] == c) rows[fill[depth[i]]++] = i;
-        if ((rc = upload_ints(&ps.rows, rows))) return rc;
+        if ((rc = dev_upload(ps.rows, rows, kPlanArray))) return rc;
         ps.compact = kind == SSS_HIP_SMOOTH_JACOBI || ps.depth <= 1;
         if (ps.compact && ps.nrows > 0 && dA && single_diag) {
             // contiguous class?  (relabeled level: F rows first, then C rows)
@@ -201,14 +191,14 @@ int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind
             sub.col_idx = cci.data();
             sub.val = cv.data();
             if ((rc = devcsr_upload(ps.sub, sub))) return rc;
-            if ((rc = upload_ints(&ps.map, cmap))) return rc;
+            if ((rc = dev_upload(ps.map, cmap, kPlanArray))) return rc;
             if (kind == SSS_HIP_SMOOTH_JACOBI) {
                 ps.y = dev_alloc<double>(cmap.size());
                 if (!ps.y) return hip_fail(hipErrorOutOfMemory, "hipMalloc(y)", __FILE__, __LINE__);
             }
         }
     }
-    if ((rc = upload_ints(&sp.cls, cls))) return rc;
+    if ((rc = dev_upload(sp.cls, cls, kPlanArray))) return rc;
     t_sched = now();
     // exact GS passes with intra-class chains: one launch per pass where the class is contiguous
     if (kind == SSS_HIP_SMOOTH_EXACT && !gcls && A.num_cols == n) {
@@ -302,14 +292,14 @@ int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind
             if ((rc = devcsr_upload(ps.ts_nl, Mn, -1, tenc, seg.data())) || (rc = devcsr_upload(ps.ts_lo, Ml, -1, tenc)))
                 return rc;
             pt.mark("ts upload");
-            if ((rc = upload_ints(&ps.ts_split, split))) return rc;
+            if ((rc = dev_upload(ps.ts_split, split, kPlanArray))) return rc;
             ps.ts_P = dev_alloc<double>((size_t)m);
             if (!ps.ts_P) return hip_fail(hipErrorOutOfMemory, "hipMalloc(P)", __FILE__, __LINE__);
         }
     }
     t_two = now();
     if (sp.pass[0].range || sp.pass[1].range)
-        if ((rc = upload_ints(&sp.diag_pos, diag_pos))) return rc;
+        if ((rc = dev_upload(sp.diag_pos, diag_pos, kPlanArray))) return rc;
     const char *nc = getenv("SSS_HIP_NOCOPY");   // 0: C/F-Jacobi through per-pass copies (tests)
     if (!(nc && *nc == '0') && kind == SSS_HIP_SMOOTH_JACOBI && !gcls && A.num_cols == n) {
         const PassSchedule &F = sp.pass[0], &Cp = sp.pass[1];
@@ -364,11 +354,11 @@ int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind
         fprintf(stderr, "[sss_hip]   smoother plan n=%d: schedule %.2f s, one-launch GS %.2f s, two-stage %.2f s, rest %.2f s\n",
                 n, t_sched - t0, t_persist - t_sched, t_two - t_persist, now() - t_two);
     if (kind == SSS_HIP_SMOOTH_JACOBI || all_diag) {   // Jacobi: row's own diagonal
-        if ((rc = upload_doubles(&sp.d_first, last_diag))) return rc;
+        if ((rc = dev_upload(sp.d_first, last_diag, kPlanArray))) return rc;
         sp.d_later = sp.d_first;
     } else {
-        if ((rc = upload_doubles(&sp.d_first, d_first_buf))) return rc;
-        if ((rc = upload_doubles(&sp.d_later, d_later_buf))) return rc;
+        if ((rc = dev_upload(sp.d_first, d_first_buf, kPlanArray))) return rc;
+        if ((rc = dev_upload(sp.d_later, d_later_buf, kPlanArray))) return rc;
     }
     return 0;
 }
@@ -1301,11 +1291,11 @@ int smoother_build_natural(SmootherPlan &sp, const SSS_MAT &A, int lo, int hi)
         ps.nrows = m;
         std::vector<int> fill(ps.h_off.begin(), ps.h_off.end()), rows(std::max(m, 1));
         for (int i = lo; i < hi; ++i) rows[fill[depth[i]]++] = i;
-        if ((rc = upload_ints(&ps.rows, rows))) return rc;
+        if ((rc = dev_upload(ps.rows, rows, kPlanArray))) return rc;
         if (ps.depth > 1 && (rc = gs_persist_build(ps, A, lo, hi, sp.long_rows, true, dir == 1))) return rc;
     }
-    if ((rc = upload_doubles(&sp.d_first, df[0])) || (rc = upload_doubles(&sp.d_later, dl[0])) ||
-        (rc = upload_doubles(&sp.nd_first, df[1])) || (rc = upload_doubles(&sp.nd_later, dl[1])))
+    if ((rc = dev_upload(sp.d_first, df[0], kPlanArray)) || (rc = dev_upload(sp.d_later, dl[0], kPlanArray)) ||
+        (rc = dev_upload(sp.nd_first, df[1], kPlanArray)) || (rc = dev_upload(sp.nd_later, dl[1], kPlanArray)))
         return rc;
     return 0;
 }

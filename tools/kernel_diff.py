@@ -43,6 +43,8 @@ def streams(path):
                 cur = out.setdefault(m.group(1), [])
         elif line.startswith(".Lfunc_end"):
             cur = None
+        elif line.startswith("__hip_cuid_"):   # the unit's id, a hash of its source, after the last data symbol
+            continue
         elif line and (not line.startswith(".") or line.endswith(":")):
             cur.append(re.sub(r"\.LBB\d+_", ".LBB_", line))   # labels carry the function's number
     return out
