@@ -130,19 +130,20 @@ def ref_units() -> dict:
     ref.SSS_blas_mv_mxy(C.byref(L0.A), C.byref(SSS_VEC(n, dptr(x))), C.byref(SSS_VEC(n, dptr(z))))
     out["bus_mxy"] = seq(z)
     for post in (0, 1):
-        u = np.cos(np.arange(n) * 0.05)
-        b = np.ones(n)
-        s = SSS_SMTR()
-        s.smoother = 2
-        s.A = C.pointer(L0.A)
-        s.b = C.pointer(SSS_VEC(n, dptr(b)))
-        s.x = C.pointer(SSS_VEC(n, dptr(u)))
-        s.nsweeps = 2
-        s.istart, s.iend, s.istep = 0, n - 1, -1 if post else 1
-        s.cf_order = 1
-        s.ordering = L0.cfmark.d
-        (ref.SSS_amg_smoother_post if post else ref.SSS_amg_smoother_pre)(C.byref(s))
-        out[f"bus_gscf_{'post' if post else 'pre'}"] = seq(u)
+        for sweeps in (2, 1, 3):   # 2: SSS_amg_pars_init's count, under the key without a suffix
+            u = np.cos(np.arange(n) * 0.05)
+            b = np.ones(n)
+            s = SSS_SMTR()
+            s.smoother = 2
+            s.A = C.pointer(L0.A)
+            s.b = C.pointer(SSS_VEC(n, dptr(b)))
+            s.x = C.pointer(SSS_VEC(n, dptr(u)))
+            s.nsweeps = sweeps
+            s.istart, s.iend, s.istep = 0, n - 1, -1 if post else 1
+            s.cf_order = 1
+            s.ordering = L0.cfmark.d
+            (ref.SSS_amg_smoother_post if post else ref.SSS_amg_smoother_pre)(C.byref(s))
+            out[f"bus_gscf_{'post' if post else 'pre'}" + ("" if sweeps == 2 else f"_s{sweeps}")] = seq(u)
     return out
 
 

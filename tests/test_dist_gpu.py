@@ -26,7 +26,9 @@ def _free_port() -> int:
 
 
 def _worker(rank, world, port, kind, n, smoother, inner_from, agg_rows, cycles, errq, transport="host", sum_order=0,
-            parts=None):
+            parts=None, sweeps=None):
+    """sweeps = (pre_iter, post_iter): put into H before either engine is built (None: the 2 and 2 of
+    SSS_amg_pars_init)."""
     try:
         os.environ["MASTER_ADDR"] = "127.0.0.1"
         os.environ["MASTER_PORT"] = str(port)
@@ -41,6 +43,10 @@ def _worker(rank, world, port, kind, n, smoother, inner_from, agg_rows, cycles, 
         from conftest import build_hierarchy, quiet_ctx
 
         H = build_hierarchy(A.generate(kind, n), quiet_ctx)
+        if sweeps is not None:
+            assert parts is None   # a partition set carries the parameters it was saved with
+            from sweep_cases import set_sweeps
+            set_sweeps(H, *sweeps)
         N = H.level(0).A.num_rows
         comm = A.Comm(world, rank, transport, device=0)
         if parts is None:
@@ -52,7 +58,9 @@ def _worker(rank, world, port, kind, n, smoother, inner_from, agg_rows, cycles, 
         assert D.nagg >= 2, D.nagg
         if kind == 7 and smoother == "hybrid" and not sum_order:
             # red-black level 0: the fused C-row residual and the dead F-row prolongation hold
-            # across the rank cut; every level's first pre-smoothing pass starts from zero
+            # across the rank cut; every level's first pre-smoothing pass starts from zero.  The flags
+            # are what the level's plan allows (sss_hip_dist_level_flags), whatever the sweep counts:
+            # the cycle itself applies the first two only with post_iter > 0 (sss_dist.hip dist_cycle_enqueue)
             f0 = D.level_flags(0)
             assert f0["fused_residual"] and f0["dead_prolong"], f0
         assert all(D.level_flags(l)["zero_first"] for l in range(D.nagg))
@@ -180,7 +188,17 @@ def test_dist_multi_peer_from_files(world, kind, n, smoother, agg, sum_order, tm
     _run(world, "host", kind, n, smoother, 2, agg, sum_order=sum_order, parts=str(tmp_path / "part"))
 
 
-def _run(world, transport, kind, n, smoother, inner_from, agg, sum_order=0, parts=None):
+@pytest.mark.parametrize("smoother,inner_from", [("hybrid", 2), ("jacobi", 0)])
+@pytest.mark.parametrize("sweeps", [(1, 1), (1, 3), (2, 0)], ids=lambda p: f"{p[0]}-{p[1]}")
+def test_dist_sweep_counts(smoother, inner_from, sweeps):
+    """pre_iter and post_iter other than 2 and 2 on the row-partitioned engine (7-pt 24^3, 2 ranks):
+    odd counts, whose two-stage passes end on the other work vector, and no post-smoothing at all,
+    where the dead F-row prolongation and the fused outer residual must stay off (sss_dist.hip
+    conditions both on post_iter > 0).  The gathered x is bitwise the single-GPU engine's."""
+    _run(2, "host", 7, 24, smoother, inner_from, 100, sweeps=sweeps)
+
+
+def _run(world, transport, kind, n, smoother, inner_from, agg, sum_order=0, parts=None, sweeps=None):
     import torch.multiprocessing as mp
 
     ctx = mp.get_context("spawn")
@@ -188,7 +206,7 @@ def _run(world, transport, kind, n, smoother, inner_from, agg, sum_order=0, part
     port = _free_port()
     procs = [ctx.Process(target=_worker,
                          args=(r, world, port, kind, n, smoother, inner_from, agg, 4, errq, transport, sum_order,
-                               parts))
+                               parts, sweeps))
              for r in range(world)]
     for p in procs:
         p.start()

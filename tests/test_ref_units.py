@@ -20,6 +20,7 @@ import amg_amd as A
 import oracle
 from amg_amd._native import SSS_IMAT, SSS_MAT, SSS_SMTR, SSS_VEC, dptr
 from conftest import BUS_MTX, build_hierarchy, oracle_solve
+from sweep_cases import banded_csr, first_f_row_lacks_diagonal
 
 HERE = Path(__file__).resolve().parent
 REFG = json.loads((HERE / "golden" / "golden.json").read_text())["ref_units"]
@@ -104,6 +105,10 @@ def test_oracle_kernels_golden(bus_matrix, quiet):
         u = np.cos(np.arange(n) * 0.05)
         ora.ora_gs_cf(dptr(u), C.byref(L0.A), dptr(np.ones(n)), 2, L0.cfmark.d, -1 if post else 1)
         assert seq(u) == REFG["bus_gscf_post" if post else "bus_gscf_pre"]
+        for sweeps in (1, 3):   # the divisor of the later sweeps not at all, and twice
+            u = np.cos(np.arange(n) * 0.05)
+            ora.ora_gs_cf(dptr(u), C.byref(L0.A), dptr(np.ones(n)), sweeps, L0.cfmark.d, -1 if post else 1)
+            assert seq(u) == REFG[f"bus_gscf_{'post' if post else 'pre'}_s{sweeps}"]
 
 
 # ---------------------------------------------------------------- live reference units
@@ -229,16 +234,23 @@ def test_coarsen_transpose_rap_vs_reference(gen, quiet):
 
 
 @needs_ref
-@pytest.mark.parametrize("gen", ["bus", "p7_12"])
+@pytest.mark.parametrize("gen", ["bus", "p7_12", "banded"])
 def test_oracle_spmv_and_smoother_vs_reference(gen, quiet):
-    M = A.read_mtx(BUS_MTX) if gen == "bus" else A.generate(7, 12)
+    """banded: 600 rows, some without a diagonal and one with a stored 0.0 (sweep_cases.banded_csr) --
+    the smoother part only, where the divisor carried over such rows matters.  Every smoother call
+    with 0, 1, 2 and 3 sweeps; 0 sweeps leave x as it was."""
+    keep = banded_csr() if gen == "banded" else None
+    M = A.read_mtx(BUS_MTX) if gen == "bus" else A.generate(7, 12) if gen == "p7_12" else keep.mat
     H = build_hierarchy(M, quiet)
+    assert H.num_levels >= 2
+    if gen == "banded":   # the divisor the first F row takes differs between sweep 0 and the later ones
+        assert first_f_row_lacks_diagonal(H.level(0))
     ora = oracle.load()
     rng = np.random.default_rng(0)
-    for l in range(H.num_levels - 1):
+    for l in range(H.num_levels - 1 if gen != "banded" else 1):   # banded: the matrix itself, level 0
         L = H.level(l)
         n = L.A.num_rows
-        for Mop in (L.A, L.P, L.R):
+        for Mop in (L.A, L.P, L.R) if gen != "banded" else ():
             x = rng.standard_normal(Mop.num_cols)
             y1 = rng.standard_normal(Mop.num_rows)
             y2 = y1.copy()
@@ -252,23 +264,31 @@ def test_oracle_spmv_and_smoother_vs_reference(gen, quiet):
             assert np.array_equal(y1.view(np.uint64), y2.view(np.uint64))
         for post in (0, 1):
             for cf in (1, 0):
-                b = rng.standard_normal(n)
-                u0 = rng.standard_normal(n)
-                us = [u0.copy(), u0.copy()]
-                for who, u in zip(("ora", "ref"), us):
-                    s = SSS_SMTR()
-                    s.smoother = 2
-                    s.A = C.pointer(L.A)
-                    s.b = C.pointer(SSS_VEC(n, dptr(b)))
-                    s.x = C.pointer(SSS_VEC(n, dptr(u)))
-                    s.nsweeps = 2
-                    s.istart, s.iend, s.istep = 0, n - 1, -1 if post else 1
-                    s.cf_order = cf
-                    s.ordering = L.cfmark.d
-                    fn = (ora.ora_smoother_post if post else ora.ora_smoother_pre) if who == "ora" else \
-                        (REF.SSS_amg_smoother_post if post else REF.SSS_amg_smoother_pre)
-                    fn(C.byref(s))
-                assert np.array_equal(us[0].view(np.uint64), us[1].view(np.uint64)), (gen, l, post, cf)
+                for nsweeps in (0, 1, 2, 3):
+                    b = rng.standard_normal(n)
+                    u0 = rng.standard_normal(n)
+                    us = [u0.copy(), u0.copy()]
+                    for who, u in zip(("ora", "ref"), us):
+                        s = SSS_SMTR()
+                        s.smoother = 2
+                        s.A = C.pointer(L.A)
+                        s.b = C.pointer(SSS_VEC(n, dptr(b)))
+                        s.x = C.pointer(SSS_VEC(n, dptr(u)))
+                        s.nsweeps = nsweeps
+                        s.istart, s.iend, s.istep = 0, n - 1, -1 if post else 1
+                        s.cf_order = cf
+                        s.ordering = L.cfmark.d
+                        fn = (ora.ora_smoother_post if post else ora.ora_smoother_pre) if who == "ora" else \
+                            (REF.SSS_amg_smoother_post if post else REF.SSS_amg_smoother_pre)
+                        fn(C.byref(s))
+                    what = (gen, l, post, cf, nsweeps)
+                    assert np.array_equal(us[0].view(np.uint64), us[1].view(np.uint64)), what
+                    assert np.isfinite(us[0]).all(), what
+                    if nsweeps == 0:
+                        assert np.array_equal(us[0].view(np.uint64), u0.view(np.uint64)), what
+                    else:   # a smoother that did nothing would agree with anything that did nothing
+                        assert not np.array_equal(us[0], u0), what
+    del keep
 
 
 @needs_ref
