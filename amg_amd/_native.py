@@ -113,7 +113,7 @@ ABI_SYMBOLS = [
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
     "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
-    "sss_hip_fgmres", "sss_hip_host_orth",
+    "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
     "SSS_amg_save", "SSS_amg_load",
     "sss_hip_coarse_solve", "sss_hip_smooth", "sss_hip_sync", "sss_hip_level_info_get", "sss_hip_num_levels", "sss_hip_tail_from",
     "sss_hip_cycle_launches", "sss_hip_cycle_bytes",
@@ -126,6 +126,7 @@ ABI_SYMBOLS = [
     "sss_hip_dist_create", "sss_hip_dist_destroy", "sss_hip_dist_info", "sss_hip_dist_level_flags",
     "sss_hip_dist_upload_vec",
     "sss_hip_dist_download_vec", "sss_hip_dist_cycle", "sss_hip_dist_residual_norm", "sss_hip_dist_sync",
+    "sss_hip_dist_pcg", "sss_hip_dist_fgmres",
     "sss_hip_dist_time_level0_spmv", "sss_hip_dist_time_levels", "sss_hip_dist_halo_stats",
     "sss_part_plan_create", "sss_part_plan_destroy", "sss_part_save", "sss_part_plan_load",
     "sss_hip_dist_create_from_files", "sss_hip_dist_level_size", "sss_part_plan_nagg", "sss_part_plan_level",
@@ -202,6 +203,9 @@ def _declare(lib):
         "sss_hip_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int, P(C.c_int), _dbl_p, _dbl_p, C.c_int]),
         "sss_hip_fgmres": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, P(C.c_int), _dbl_p, _dbl_p, C.c_int]),
         "sss_hip_host_orth": (C.c_int, [C.c_int, C.c_int, _dbl_p, _dbl_p, _dbl_p, _dbl_p]),
+        "sss_hip_host_pcg_update": (C.c_int, [C.c_int, C.c_double, C.c_double, _dbl_p, _dbl_p, _dbl_p, _dbl_p, _dbl_p,
+                                              _dbl_p]),
+        "sss_hip_host_dot2": (C.c_int, [C.c_int, _dbl_p, _dbl_p, _dbl_p, _dbl_p]),
         "SSS_amg_save": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "SSS_amg_load": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "sss_hip_coarse_solve": (C.c_int, [C.c_void_p]),
@@ -241,6 +245,9 @@ def _declare(lib):
         "sss_hip_dist_download_vec": (C.c_int, [C.c_void_p, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_dist_cycle": (C.c_int, [C.c_void_p]),
         "sss_hip_dist_residual_norm": (C.c_int, [C.c_void_p, _dbl_p]),
+        "sss_hip_dist_pcg": (C.c_int, [C.c_void_p, C.c_double, C.c_int, P(C.c_int), _dbl_p, _dbl_p, C.c_int]),
+        "sss_hip_dist_fgmres": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, P(C.c_int), _dbl_p, _dbl_p,
+                                          C.c_int]),
         "sss_hip_dist_sync": (C.c_int, [C.c_void_p]),
         "sss_hip_dist_time_level0_spmv": (C.c_int, [C.c_void_p, C.c_int, _dbl_p]),
         "sss_hip_dist_time_levels": (C.c_int, [C.c_void_p, C.c_int, _dbl_p, _dbl_p, C.c_int]),
@@ -852,6 +859,25 @@ class DistHierarchy:
         r = C.c_double()
         self._check(lib().sss_hip_dist_residual_norm(self.d, C.byref(r)), "dist residual")
         return r.value
+
+    def pcg(self, tol: float, maxit: int = 100):
+        """AMG-preconditioned CG over all ranks (b, x uploaded as for cycle(); collective: every rank
+        calls it); returns (iterations, relative residual history), the same on every rank."""
+        hist = np.zeros(max(maxit, 1))
+        its, rel = C.c_int(), C.c_double()
+        self._check(lib().sss_hip_dist_pcg(self.d, tol, maxit, C.byref(its), C.byref(rel), dptr(hist), len(hist)),
+                    "dist pcg")
+        return its.value, hist[: its.value].copy()
+
+    def fgmres(self, tol: float, restart: int = 20, maxit: int = 100):
+        """AMG-preconditioned flexible GMRES(restart) over all ranks, for operators that are not
+        symmetric positive definite (collective); returns (iterations, history of the relative
+        residual estimate), the same on every rank."""
+        hist = np.zeros(max(maxit, 1))
+        its, rel = C.c_int(), C.c_double()
+        self._check(lib().sss_hip_dist_fgmres(self.d, tol, restart, maxit, C.byref(its), C.byref(rel), dptr(hist),
+                                              len(hist)), "dist fgmres")
+        return its.value, hist[: its.value].copy()
 
     def sync(self):
         self._check(lib().sss_hip_dist_sync(self.d), "dist sync")

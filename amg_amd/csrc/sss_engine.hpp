@@ -660,6 +660,14 @@ int launch_axpy_ratio(int n, const double *num, const double *den, double sign, 
 // p = z + ((*num - *numold) / *den) * p   (numold null: *num / *den)
 int launch_xpby_ratio(int n, const double *num, const double *numold, const double *den, const double *z, double *p,
                       hipStream_t s);
+// One pass of a CG iteration (a = *num / *den on the device): x += a p, r_old = r, r -= a q, and
+// partial[0 .. 1024) = fixed-order partials of the new r.r (sum them with launch_final_sum: partial
+// holds 1024 + kFinalScratch doubles).  Elementwise results are launch_axpy_ratio's bit for bit.
+int launch_pcg_update(int n, const double *num, const double *den, const double *p, const double *q, double *x,
+                      double *r, double *r_old, double *partial, hipStream_t s);
+// partial[0 .. 1024) = partials of r.z, partial[1024 .. 2048) = of r_old.z, in one pass over z (sum
+// them with launch_multi_final(2, partial, out, ...)).
+int launch_dot2(int n, const double *r, const double *r_old, const double *z, double *partial, hipStream_t s);
 
 // ---- multi-vector orthogonalisation for the flexible GMRES (sss_fgmres.hip) ------------------
 // V: k columns back to back with leading dimension ld >= n (ld even, V and w 16-byte aligned).

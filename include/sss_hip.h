@@ -271,6 +271,13 @@ int sss_hip_host_smooth(const SSS_SMTR *s, int post);
  * columns of n doubles back to back; w is orthogonalised against them in place (not normalised),
  * hcol[0 .. k) receives the Hessenberg coefficients and *norm the 2-norm of the new w. */
 int sss_hip_host_orth(int n, int k, const double *V, double *w, double *hcol, double *norm);
+/* The two fused level-0 kernels of sss_hip_dist_pcg on host data.  pcg_update: with a = alpha_num /
+ * alpha_den, x += a p and r -= a q in place, r_old = the old r, *rr = the sum of squares of the new
+ * r -- one pass; the elementwise results are those of the unfused updates bit for bit.  dot2:
+ * out[0] = r . z and out[1] = r_old . z in one pass over z.  Sums are fixed-order (deterministic). */
+int sss_hip_host_pcg_update(int n, double alpha_num, double alpha_den, const double *p, const double *q, double *x,
+                            double *r, double *r_old, double *rr);
+int sss_hip_host_dot2(int n, const double *r, const double *r_old, const double *z, double *out);
 /* The three host-memory entry points keep the device form of their operator (keyed by a content
  * hash of the CSR arrays, the use and the device) in a small cache, so a caller that loops over
  * them with the same matrix uploads it once; this releases the cached device objects. */
@@ -344,6 +351,30 @@ int sss_hip_dist_download_vec(sss_hip_dist *d, int which, double *own, int n);
 int sss_hip_dist_cycle(sss_hip_dist *d);
 /* global ||b0 - A0 x0||_2 (one 8-byte allreduce), synchronises */
 int sss_hip_dist_residual_norm(sss_hip_dist *d, double *absres);
+/* sss_hip_pcg and sss_hip_fgmres on the row-partitioned engine: the same recurrences (flexible CG
+ * with the Polak-Ribiere beta; right-preconditioned FGMRES(restart) with classical Gram-Schmidt
+ * applied twice), stop rules, hist / hist_cap / NULL rules and treatment of ||b|| = 0, restart < 1
+ * (ERROR_INPUT_PAR, before any collective) and a non-finite norm, with "level-0 b / x vector" read
+ * as this rank's own rows of them; b is restored on return.  Collective: every rank calls with the
+ * same arguments.  z = one sss_hip_dist_cycle on (r, 0) (the captured graph where there is one);
+ * A p and A z use the level-0 local matrix after a halo exchange of the vector.  Every dot product is
+ * summed over the ranks before use and every branch is taken from reduced values only, so all ranks
+ * leave in the same iteration -- also with ERROR_MISC when a one-launch Gauss-Seidel pass stalled
+ * on any rank (the stall word rides on one of the reductions).
+ * Reductions per iteration -- PCG: 3 (p.q; r.r with the stall flag; {r.z, r_old.z} together), plus
+ * ||b||^2 and the first r.z once per solve.  FGMRES: 3 per Arnoldi step (the coefficients of the
+ * first and of the second Gram-Schmidt pass; ||w||^2 with the stall flag -- the Hessenberg column is
+ * formed from the reduced coefficients and the root taken after the reduction), plus ||b||^2 once
+ * and ||r||^2 at every restart.  Over RCCL the scalars stay on the device (in-place ncclAllReduce on
+ * the engine stream) with one small read-back per iteration; over the host transport each reduction
+ * synchronises and goes through allreduce_sum; the timing communicator skips them.
+ * The iterates are not bitwise the single-GPU solvers': the dot products are summed in another
+ * order; every elementwise operation and the whole preconditioner are the same bit for bit.
+ * Workspace is allocated at first use (FGMRES: regrown when restart grows) and freed with the
+ * engine: PCG 5 vectors of this rank's rows, FGMRES 2 restart + 3. */
+int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *iters, double *relres, double *hist, int hist_cap);
+int sss_hip_dist_fgmres(sss_hip_dist *d, double tol, int restart, int maxit, int *iters, double *relres, double *hist,
+                        int hist_cap);
 int sss_hip_dist_sync(sss_hip_dist *d);
 /* average ms of `reps` local level-0 residual SpMVs (no exchange): the per-rank roofline */
 int sss_hip_dist_time_level0_spmv(sss_hip_dist *d, int reps, double *avg_ms);
