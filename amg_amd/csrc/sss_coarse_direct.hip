@@ -10,13 +10,18 @@
 // rank-1 elimination kernel per column, column unscramble at the end).  Apply: one wave per
 // row of the inverse, coalesced 8-B loads along the row, shuffle reduction — HBM/MALL-bound
 // (n^2 * 8 B per cycle: 203 MB at n = 5,041).
+//
+// A singular or non-finite matrix has no inverse to apply: a pivot that is zero or not finite, and
+// any non-finite entry of the finished inverse (a NaN is never the maximum of a pivot search, so it
+// can pass every pivot and still spread), set one device word that the build reads once after the
+// last kernel; the build then fails with ERROR_SOLVER_EXIT and leaves no inverse behind.
 #include "sss_engine.hpp"
 
 #include <vector>
 
 namespace sss {
 
-__global__ __launch_bounds__(1024) void gj_pivot(double *M, int n, int k, double *colbuf, int *swaps)
+__global__ __launch_bounds__(1024) void gj_pivot(double *M, int n, int k, double *colbuf, int *swaps, int *bad)
 {
     __shared__ double s_best[1024 / 64];
     __shared__ int s_idx[1024 / 64];
@@ -54,6 +59,7 @@ __global__ __launch_bounds__(1024) void gj_pivot(double *M, int n, int k, double
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 1024) colbuf[i] = M[(size_t)i * n + k];
     __syncthreads();
+    if (threadIdx.x == 0 && !(fabs(colbuf[k]) > 0.0 && isfinite(colbuf[k]))) *bad = 1;
     const double inv = 1.0 / colbuf[k];
     for (int j = threadIdx.x; j < n; j += 1024) M[(size_t)k * n + j] = (j == k) ? inv : M[(size_t)k * n + j] * inv;
 }
@@ -66,6 +72,15 @@ __global__ __launch_bounds__(256) void gj_eliminate(double *M, int n, int k, con
     const double f = colbuf[i];
     if (j == k) M[(size_t)i * n + k] = -f * M[(size_t)k * n + k];
     else M[(size_t)i * n + j] -= f * M[(size_t)k * n + j];
+}
+
+// the scan of the finished inverse: a non-finite entry sets *bad (grid-stride, coalesced)
+__global__ __launch_bounds__(256) void gj_scan(const double *__restrict__ M, size_t total, int *bad)
+{
+    bool finite = true;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256)
+        finite = finite && isfinite(M[e]);
+    if (!finite) *bad = 1;
 }
 
 __global__ __launch_bounds__(256) void gj_unscramble(double *M, int n, const int *__restrict__ swaps)
@@ -106,23 +121,33 @@ int coarse_direct_build(CoarseDirect &cd, const SSS_MAT &A, hipStream_t s)
     cd.inv = dev_alloc<double>((size_t)n * n);
     double *colbuf = dev_alloc<double>((size_t)n);
     int *swaps = dev_alloc<int>((size_t)n);
-    if (!cd.inv || !colbuf || !swaps) {
-        dev_free(colbuf);
-        dev_free(swaps);
-        return hip_fail(hipErrorOutOfMemory, "hipMalloc(coarse inverse)", __FILE__, __LINE__);
-    }
-    SSS_HIP(hipMemcpyAsync(cd.inv, dense.data(), sizeof(double) * dense.size(), hipMemcpyHostToDevice, s));
-    const dim3 egrid((n + 255) / 256, n);
-    for (int k = 0; k < n; ++k) {
-        hipLaunchKernelGGL(gj_pivot, dim3(1), dim3(1024), 0, s, cd.inv, n, k, colbuf, swaps);
-        hipLaunchKernelGGL(gj_eliminate, egrid, dim3(256), 0, s, cd.inv, n, k, colbuf);
-    }
-    hipLaunchKernelGGL(gj_unscramble, dim3((n + 255) / 256), dim3(256), 0, s, cd.inv, n, swaps);
-    SSS_HIP(hipGetLastError());
-    SSS_HIP(hipStreamSynchronize(s));
+    int *d_bad = dev_alloc<int>(1);   // the singular / non-finite word
+    int bad = 0;
+    auto run = [&]() -> int {
+        if (!cd.inv || !colbuf || !swaps || !d_bad)
+            return hip_fail(hipErrorOutOfMemory, "hipMalloc(coarse inverse)", __FILE__, __LINE__);
+        SSS_HIP(hipMemcpyAsync(cd.inv, dense.data(), sizeof(double) * dense.size(), hipMemcpyHostToDevice, s));
+        SSS_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        const dim3 egrid((n + 255) / 256, n);
+        for (int k = 0; k < n; ++k) {
+            hipLaunchKernelGGL(gj_pivot, dim3(1), dim3(1024), 0, s, cd.inv, n, k, colbuf, swaps, d_bad);
+            hipLaunchKernelGGL(gj_eliminate, egrid, dim3(256), 0, s, cd.inv, n, k, colbuf);
+        }
+        const size_t total = (size_t)n * n;
+        const unsigned sgrid = (unsigned)std::min<size_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL(gj_scan, dim3(sgrid), dim3(256), 0, s, cd.inv, total, d_bad);
+        hipLaunchKernelGGL(gj_unscramble, dim3((n + 255) / 256), dim3(256), 0, s, cd.inv, n, swaps);
+        SSS_HIP(hipGetLastError());
+        SSS_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        SSS_HIP(hipStreamSynchronize(s));
+        return bad ? ERROR_SOLVER_EXIT : 0;
+    };
+    const int rc = run();
     dev_free(colbuf);
     dev_free(swaps);
-    return 0;
+    dev_free(d_bad);
+    if (rc) coarse_direct_free(cd);
+    return rc;
 }
 
 void coarse_direct_free(CoarseDirect &cd)

@@ -1083,6 +1083,7 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
             (rc = kr_fetch(d, S + NB2, Hh + NB2, 1)))
             return rc;
         const double nb = std::sqrt(Hh[NB2]);   // the global ||b||: the same on every rank
+        if (!std::isfinite(nb)) return ERROR_SOLVER_EXIT;
         if (nb == 0.0) {
             SSS_HIP(hipMemsetAsync(xs, 0, bytes, s));
             return 0;
@@ -1090,6 +1091,16 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
         if (maxit < 1) return 0;
         if ((rc = residual(d, 0, false, nullptr))) return rc;   // wp = b - A x
         SSS_HIP(hipMemcpyAsync(r, L.wp, bytes, hipMemcpyDeviceToDevice, s));
+        // the global ||r_0||^2, one reduction before the loop: zero (x solves the system exactly; z = 0
+        // would make the first step length 0 / 0) and non-finite leave here, on every rank alike
+        if ((rc = launch_dot(m, r, r, part, S + RR, s)) || (rc = kr_reduce(d, S + RR, Hh + RR, 1)) ||
+            (rc = kr_fetch(d, S + RR, Hh + RR, 1)))
+            return rc;
+        if (!std::isfinite(Hh[RR])) return ERROR_SOLVER_EXIT;
+        if (Hh[RR] == 0.0) {
+            rel = 0.0;
+            return 0;
+        }
         if ((rc = kr_precondition(d))) return rc;
         if ((rc = launch_dot(m, r, z, part, S + RZ, s)) || (rc = kr_reduce(d, S + RZ, Hh + RZ, 1))) return rc;
         SSS_HIP(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, s));
@@ -1103,6 +1114,7 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
             if ((rc = launch_err_flag(d->d_err, S + STALL, s))) return rc;
             if ((rc = kr_reduce(d, S + RR, Hh + RR, 2)) || (rc = kr_fetch(d, S + RR, Hh + RR, 2))) return rc;
             if (Hh[STALL] != 0.0) return kr_stalled(d, "sss_hip_dist_pcg");
+            if (!std::isfinite(Hh[RR])) return ERROR_SOLVER_EXIT;
             rel = std::sqrt(Hh[RR]) / nb;
             if (hist && it <= hist_cap) hist[it - 1] = rel;
             if (rel < tol || it >= maxit) return 0;

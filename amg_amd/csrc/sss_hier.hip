@@ -642,8 +642,19 @@ static sss_hip_hier *hb_finish(HierBuild &b)
     h->coarse_mode = h->opts.coarse;
     if (h->coarse_mode == SSS_HIP_COARSE_DIRECT && Ac.num_rows > 20000) h->coarse_mode = SSS_HIP_COARSE_KRYLOV;
     if (h->coarse_mode == SSS_HIP_COARSE_DIRECT) {
-        if (coarse_direct_build(h->direct, Ac, h->stream)) return fail("coarse inverse");
-    } else {
+        // a singular or non-finite coarsest matrix has no inverse: the Krylov coarse solve instead,
+        // as above 20,000 rows (and no single-workgroup tail, which ends in the inverse)
+        const int rc = coarse_direct_build(h->direct, Ac, h->stream);
+        if (rc == ERROR_SOLVER_EXIT) {
+            h->coarse_mode = SSS_HIP_COARSE_KRYLOV;
+            if (h->opts.verbose)
+                fprintf(stderr, "[sss_hip] coarsest matrix (n=%d) is singular or not finite: Krylov coarse solve\n",
+                        Ac.num_rows);
+        } else if (rc) {
+            return fail("coarse inverse");
+        }
+    }
+    if (h->coarse_mode != SSS_HIP_COARSE_DIRECT) {
         h->krylov = coarse_krylov_create(h->L[h->nl - 1].A, h->opts.row_cap, h->stream);
         if (!h->krylov) return fail("coarse Krylov workspace");
     }
@@ -1236,9 +1247,13 @@ extern "C" int sss_hip_residual_norm(sss_hip_hier *h, double *absres)
 // configured smoothers and coarse solve) per iteration as M^-1.  Right-hand side L0.b, initial
 // guess and result L0.x; iterates until ||r_k|| / ||b|| < tol (recursive residual) or maxit.
 // Dots are fixed-order reductions (deterministic); one 8-byte read-back per iteration.
+// ||b|| = 0: x = 0, no iteration.  ||r_0|| = 0 exactly: x is left as it is, no iteration (z = 0 would
+// make the first step length 0 / 0).  A non-finite ||b||, ||r_0|| or r_k . r_k: ERROR_SOLVER_EXIT with
+// b restored and the last finite iterate in x (x_k is formed only after r_k . r_k has been read).
 extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, double *relres, double *hist,
                            int hist_cap)
 {
+    if (!h) return ERROR_INPUT_PAR;
     auto &L = h->L[0];
     const int n = L.A.n;
     hipStream_t s = h->stream;
@@ -1274,21 +1289,31 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
     if ((rc = launch_dot(n, bs, bs, h->pcg_part, rr, s)) || (rc = fetch(rr, &nb2))) return rc;
     const double nb = std::sqrt(nb2);
     int it = 0;
-    if (nb == 0.0) {
-        SSS_HIP(hipMemsetAsync(L.x, 0, bytes, s));
-    } else {
+    auto solve = [&]() -> int {
+        if (!std::isfinite(nb)) return ERROR_SOLVER_EXIT;
+        if (nb == 0.0) {
+            SSS_HIP(hipMemsetAsync(xs, 0, bytes, s));
+            return 0;
+        }
         if ((rc = launch_spmv(L.A, SSS_HIP_SPMV_RESID, -1.0, xs, bs, r, 0, nullptr, s))) return rc;   // r = b - A x
+        if ((rc = launch_dot(n, r, r, h->pcg_part, rr, s)) || (rc = fetch(rr, &rr_h))) return rc;
+        if (!std::isfinite(rr_h)) return ERROR_SOLVER_EXIT;
+        if (rr_h == 0.0) {   // x solves the system exactly
+            rel = 0.0;
+            return 0;
+        }
         if ((rc = precondition(r, z))) return rc;
         if ((rc = launch_dot(n, r, z, h->pcg_part, rz, s))) return rc;
         SSS_HIP(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, s));
         while (it < maxit) {
-            ++it;
             if ((rc = launch_spmv(L.A, SSS_HIP_SPMV_MXY, 1.0, p, nullptr, q, 0, nullptr, s))) return rc;   // q = A p
             if ((rc = launch_dot(n, p, q, h->pcg_part, pq, s))) return rc;
-            if ((rc = launch_axpy_ratio(n, rz, pq, 1.0, p, xs, s))) return rc;                          // x += a p
             SSS_HIP(hipMemcpyAsync(ro, r, bytes, hipMemcpyDeviceToDevice, s));
             if ((rc = launch_axpy_ratio(n, rz, pq, -1.0, q, r, s))) return rc;                          // r -= a q
             if ((rc = launch_dot(n, r, r, h->pcg_part, rr, s)) || (rc = fetch(rr, &rr_h))) return rc;
+            if (!std::isfinite(rr_h)) return ERROR_SOLVER_EXIT;   // before x takes the step
+            ++it;
+            if ((rc = launch_axpy_ratio(n, rz, pq, 1.0, p, xs, s))) return rc;                          // x += a p
             rel = std::sqrt(rr_h) / nb;
             if (hist && it <= hist_cap) hist[it - 1] = rel;
             if (rel < tol) break;
@@ -1298,13 +1323,17 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
             if ((rc = launch_xpby_ratio(n, rzn, roz, rz, z, p, s))) return rc;   // p = z + ((r-ro).z / rz) p
             SSS_HIP(hipMemcpyAsync(rz, rzn, sizeof(double), hipMemcpyDeviceToDevice, s));
         }
-        SSS_HIP(hipMemcpyAsync(L.x, xs, bytes, hipMemcpyDeviceToDevice, s));
-    }
+        return 0;
+    };
+    rc = solve();
+    // the iterate and the caller's b back (after an error: the last finite iterate)
+    SSS_HIP(hipMemcpyAsync(L.x, xs, bytes, hipMemcpyDeviceToDevice, s));
     SSS_HIP(hipMemcpyAsync(L.b, bs, bytes, hipMemcpyDeviceToDevice, s));
     SSS_HIP(hipStreamSynchronize(s));
     h->resid_c_ready = false;
     if (iters) *iters = it;
     if (relres) *relres = rel;
+    if (rc) return rc;
     return hier_stall_check(h);
 }
 
@@ -1910,12 +1939,16 @@ extern "C" int sss_hip_host_coarse_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, dou
     if (sss_hip_device_count() <= 0) return ERROR_MISC;
     const int n = A->num_rows;
     const bool direct = coarse_mode == SSS_HIP_COARSE_DIRECT && n <= 20000;
+    int build_rc = ERROR_MISC;   // a singular or non-finite matrix: the inverse's own code
     auto M = prepared().get<HostCoarse>(
         matrix_key(*A, mix64(mix64(0x4353ull, direct ? 1 : 0), (unsigned long long)row_cap)), [&] {
             auto m = std::make_shared<HostCoarse>();
             if (devcsr_upload(m->d, *A)) return std::shared_ptr<HostCoarse>();
             if (direct) {
-                if (coarse_direct_build(m->cd, *A, nullptr)) return std::shared_ptr<HostCoarse>();
+                if (int rc = coarse_direct_build(m->cd, *A, nullptr)) {
+                    build_rc = rc;
+                    return std::shared_ptr<HostCoarse>();
+                }
                 m->direct = true;
             } else {
                 m->k = coarse_krylov_create(m->d, row_cap, nullptr);
@@ -1923,7 +1956,7 @@ extern "C" int sss_hip_host_coarse_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, dou
             }
             return m;
         }, cacheable(*A));
-    if (!M) return ERROR_MISC;
+    if (!M) return build_rc;
     std::lock_guard<std::mutex> run_lock(M->run);
     double *dx = dev_alloc<double>((size_t)n), *db = dev_alloc<double>((size_t)n);
     int rc = (!dx || !db) ? ERROR_ALLOC_MEM : 0;

@@ -171,7 +171,10 @@ int SSS_amg_load(SSS_AMG *mg, const char *path);
  * reference's Krylov solvers serve only the coarsest level): right-hand side = the level-0 b
  * vector, initial guess / result = the level-0 x vector, one V-cycle per iteration as the
  * preconditioner.  Stops when ||r_k||/||b|| < tol or after maxit iterations; hist (optional)
- * receives the relative residual of each iteration. */
+ * receives the relative residual of each iteration.  b is restored on return.  ||b|| = 0: x = 0, no
+ * iteration.  ||b - A x0|| = 0 exactly: no iteration, x untouched, relres 0.  h == NULL:
+ * ERROR_INPUT_PAR; a non-finite ||b||, ||b - A x0|| or r_k . r_k: ERROR_SOLVER_EXIT, with the last
+ * finite iterate in x. */
 int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, double *relres, double *hist, int hist_cap);
 /* AMG-preconditioned flexible GMRES(restart) on level 0, for operators that are not symmetric
  * positive definite (an engine extension, like sss_hip_pcg): right preconditioning with one V-cycle
@@ -282,6 +285,9 @@ int sss_hip_host_dot2(int n, const double *r, const double *r_old, const double 
  * hash of the CSR arrays, the use and the device) in a small cache, so a caller that loops over
  * them with the same matrix uploads it once; this releases the cached device objects. */
 void sss_hip_host_cache_clear(void);
+/* coarse_mode SSS_HIP_COARSE_DIRECT (up to 20,000 rows): the explicit inverse; a matrix with a zero
+ * or non-finite pivot, or whose inverse has a non-finite entry, gives ERROR_SOLVER_EXIT and leaves x
+ * untouched (sss_hip_hier_create falls back to the Krylov coarse solve for such a coarsest level). */
 int sss_hip_host_coarse_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, double ctol, int coarse_mode,
                               int row_cap);
 
@@ -362,7 +368,8 @@ int sss_hip_dist_residual_norm(sss_hip_dist *d, double *absres);
  * leave in the same iteration -- also with ERROR_MISC when a one-launch Gauss-Seidel pass stalled
  * on any rank (the stall word rides on one of the reductions).
  * Reductions per iteration -- PCG: 3 (p.q; r.r with the stall flag; {r.z, r_old.z} together), plus
- * ||b||^2 and the first r.z once per solve.  FGMRES: 3 per Arnoldi step (the coefficients of the
+ * ||b||^2, ||r_0||^2 and the first r.z once per solve (after a non-finite r.r the iterate in x is
+ * the last one formed: x and r take their step in one kernel).  FGMRES: 3 per Arnoldi step (the coefficients of the
  * first and of the second Gram-Schmidt pass; ||w||^2 with the stall flag -- the Hessenberg column is
  * formed from the reduced coefficients and the root taken after the reduction), plus ||b||^2 once
  * and ||r||^2 at every restart.  Over RCCL the scalars stay on the device (in-place ncclAllReduce on

@@ -165,6 +165,46 @@ def _sc_zero_rhs(c):
     assert its == 0 and len(hist) == 0 and not x.any()
 
 
+def _sc_exact_guess(c):
+    """r0 = 0 exactly (b = A 1 in small integers, x0 = 1): no iteration on any rank, relres 0, x
+    untouched -- not the step length 0 / 0 and maxit cycles on NaN vectors."""
+    import oracle
+    from amg_amd._native import dptr
+    b = np.zeros(c.N)
+    oracle.load().ora_mv_mxy(C.byref(c.H.level(0).A), dptr(np.ones(c.N)), dptr(b))
+    assert b.any()
+    its, hist, x = c.solve_dist(b, np.ones(c.N))
+    assert its == 0 and len(hist) == 0
+    assert np.array_equal(_u64(x), _u64(np.ones(c.N)))
+    c.D.upload("b", b[c.lo:c.hi])
+    c.D.upload("x", np.ones(c.hi - c.lo))
+    n_it, rel = C.c_int(-1), C.c_double(-1.0)
+    assert c.A.lib().sss_hip_dist_pcg(c.D.d, c.tol, 100, C.byref(n_it), C.byref(rel), None, 0) == 0
+    assert n_it.value == 0 and rel.value == 0.0
+
+
+def _sc_nonfinite_rhs(c):
+    """One NaN in b, on rank 0's rows only: the other ranks see it in the reduced ||b|| alone.  Every
+    rank returns ERROR_SOLVER_EXIT in the same iteration, x the initial guess, b back as it was."""
+    b, x0 = c.rhs(), c.rhs(2)
+    ranges = [None] * c.world
+    c.dist.all_gather_object(ranges, (c.rank, c.lo, c.hi))
+    lo0, hi0 = next((lo, hi) for r, lo, hi in ranges if r == 0)
+    b[(lo0 + hi0) // 2] = np.nan
+    c.D.upload("b", b[c.lo:c.hi])
+    c.D.upload("x", x0[c.lo:c.hi])
+    its, rel = C.c_int(-1), C.c_double(-1.0)
+    rc = c.A.lib().sss_hip_dist_pcg(c.D.d, c.tol, 100, C.byref(its), C.byref(rel), None, 0)
+    got = [None] * c.world
+    c.dist.all_gather_object(got, (rc, its.value))
+    assert all(g == got[0] for g in got), got
+    assert rc == -49 and its.value <= 1, (rc, its.value)   # ERROR_SOLVER_EXIT
+    assert np.array_equal(_u64(c.D.download("x")), _u64(x0[c.lo:c.hi]))
+    assert np.array_equal(_u64(c.D.download("b")), _u64(b[c.lo:c.hi]))
+    with pytest.raises(RuntimeError):
+        c.D.pcg(c.tol)
+
+
 def _sc_pcg_edges(c):
     """maxit = 3; hist_cap = 1 and hist = NULL through raw ctypes."""
     from amg_amd._native import dptr
@@ -234,8 +274,8 @@ def _sc_fgmres_edges(c):
         c.compare(got, ref, b, "fgmres", "maxit 4, restart 3", margin=False)
 
 
-SCENARIOS = {f.__name__[4:]: f for f in (_sc_solve, _sc_one_sided, _sc_zero_rhs, _sc_pcg_edges, _sc_engine_state,
-                                          _sc_deterministic, _sc_fgmres_edges)}
+SCENARIOS = {f.__name__[4:]: f for f in (_sc_solve, _sc_one_sided, _sc_zero_rhs, _sc_exact_guess, _sc_nonfinite_rhs,
+                                          _sc_pcg_edges, _sc_engine_state, _sc_deterministic, _sc_fgmres_edges)}
 
 
 def _worker(rank, world, port, cfg, errq):
@@ -329,6 +369,14 @@ def test_pcg_one_sided_rhs():
 
 def test_pcg_zero_rhs():
     _run(2, kind=7, n=24, smoother="hybrid", agg=100, scenario="zero_rhs")
+
+
+def test_pcg_exact_initial_guess():
+    _run(2, kind=7, n=24, smoother="hybrid", agg=100, scenario="exact_guess")
+
+
+def test_pcg_nonfinite_rhs():
+    _run(2, kind=7, n=24, smoother="hybrid", agg=100, scenario="nonfinite_rhs")
 
 
 def test_pcg_stop_and_history_edges():
