@@ -15,8 +15,6 @@
 #include "sss_engine.hpp"
 #include "sss_spmv_dev.hpp"
 
-#include <cstdint>
-
 namespace sss {
 
 constexpr int kDotBlocks = 1024;   // partial sums per dot (fills the chip, fixed order)
@@ -76,17 +74,8 @@ int launch_xpby_ratio(int n, const double *num, const double *numold, const doub
     return 0;
 }
 
-static_assert(kDotBlocks == kOrthBlocks, "dot2's partials are summed by launch_multi_final");
-
-// The chunk of workgroup b of kDotBlocks: [lo, hi), lo even so that 16-byte accesses stay aligned.
-__device__ __forceinline__ void dot_chunk(int n, int &lo, int &hi)
-{
-    int per = (n + kDotBlocks - 1) / kDotBlocks;
-    per += per & 1;
-    const long long a = (long long)blockIdx.x * per;
-    lo = a < n ? (int)a : n;
-    hi = a + per < n ? (int)(a + per) : n;
-}
+// dot2's partials are summed by launch_multi_final, and the fused kernels take dot_chunk's chunks
+static_assert(kDotBlocks == kOrthBlocks, "one fixed grid for the fused BLAS-1 and the orthogonalisation");
 
 // a = *num / *den:  x += a p,  r_old = r,  r += (-a) q,  partial[block] = sum of the new r[i]^2 over
 // the block's chunk.  V2: every vector is 16-byte aligned (two rows per access).
@@ -168,8 +157,6 @@ __global__ __launch_bounds__(kBlock) void dot2_partials(int n, const double *__r
     }
 }
 
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 int launch_pcg_update(int n, const double *num, const double *den, const double *p, const double *q, double *x,
                       double *r, double *r_old, double *partial, hipStream_t s)
 {
@@ -245,7 +232,7 @@ extern "C" int sss_hip_host_dot2(int n, const double *r, const double *r_old, co
                 hipMemcpy(v + 2 * ld, z, bytes, hipMemcpyHostToDevice) != hipSuccess))
         rc = ERROR_MISC;
     if (!rc) rc = launch_dot2(n, v, v + ld, v + 2 * ld, part, nullptr);
-    if (!rc) rc = launch_multi_final(2, part, sc, nullptr, true, nullptr);
+    if (!rc) rc = launch_multi_final(2, part, sc, nullptr);
     if (!rc && hipMemcpy(out, sc, 2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
     dev_free(v);
     dev_free(part);
@@ -285,7 +272,7 @@ extern "C" int sss_lab_time_pcg_fused(int n, int reps, double *fused_ms, double 
                 if (!rc) rc = launch_pcg_update(n, sc, sc + 1, p, q, x, r, ro, part, nullptr);
                 if (!rc) rc = launch_final_sum(part, kDotBlocks, sc + 2, false, nullptr);
                 if (!rc) rc = launch_dot2(n, r, ro, z, part, nullptr);
-                if (!rc) rc = launch_multi_final(2, part, sc + 3, nullptr, true, nullptr);
+                if (!rc) rc = launch_multi_final(2, part, sc + 3, nullptr);
             } else {
                 if (!rc) rc = launch_axpy_ratio(n, sc, sc + 1, 1.0, p, x, nullptr);
                 if (!rc && hipMemcpyAsync(ro, r, bytes, hipMemcpyDeviceToDevice, nullptr) != hipSuccess) rc = ERROR_MISC;

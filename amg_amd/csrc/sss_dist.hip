@@ -146,11 +146,7 @@ struct sss_hip_dist {
     double *kr_s = nullptr;      // pcg: device scalars
     double *kr_h = nullptr;      // ... their pinned host mirror
     double *pcg_v = nullptr;     // saved b, iterate x, q, r_old (own rows each), p (own rows + ghosts)
-    double *fg_v = nullptr;      // 2 fg_m + 3 vectors: V (fg_m + 1), Z (fg_m), saved b, iterate x
-    double *fg_part = nullptr;   // orth_part_doubles(fg_m)
-    double *fg_s = nullptr;      // c1, c2 (fg_m each), {||w||^2, stall}, Hessenberg column + norm + stall, y
-    double *fg_h = nullptr;      // pinned host mirror of fg_s
-    int fg_m = 0;                // the largest restart so far
+    FgmresWork fg;
 };
 
 namespace {
@@ -402,22 +398,12 @@ int allreduce_norm(sss_hip_dist *d)
     return 0;
 }
 
-void fgmres_free(sss_hip_dist *d)
-{
-    dev_free(d->fg_v);
-    dev_free(d->fg_part);
-    dev_free(d->fg_s);
-    if (d->fg_h) (void)hipHostFree(d->fg_h);
-    d->fg_v = d->fg_part = d->fg_s = d->fg_h = nullptr;
-    d->fg_m = 0;
-}
-
 void release(sss_hip_dist *d)
 {
     if (!d) return;
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     if (d->cycle_exec) (void)hipGraphExecDestroy(d->cycle_exec);
-    fgmres_free(d);
+    d->fg.release();
     dev_free(d->pcg_v);
     dev_free(d->kr_part);
     dev_free(d->kr_s);
@@ -972,79 +958,87 @@ extern "C" int sss_hip_dist_residual_norm(sss_hip_dist *d, double *absres)
 
 // ---- AMG-preconditioned Krylov solvers on the row-partitioned engine ---------------------------
 // sss_hip_pcg / sss_hip_fgmres (sss_hier.hip) with every level-0 vector cut to this rank's rows:
-// the same recurrences and stop rules, z = one sss_hip_dist_cycle on (r, 0), A v with a halo
-// exchange of v, and every dot product summed over the ranks before it is used.  Every branch and
-// loop exit is taken from reduced values only, so all ranks leave in the same iteration.
+// the same stop rules (FGMRES: the same loop, fgmres_solve of sss_fgmres.hip), z = one
+// sss_hip_dist_cycle on (r, 0), A v with a halo exchange of v, and every dot product summed over the
+// ranks before it is used.  Every branch and loop exit is taken from reduced values only, so all
+// ranks leave in the same iteration.
 namespace {
 
-// dv[0 .. n) summed over the ranks, in place on the device.  RCCL: enqueued on the engine stream,
-// nothing comes to the host.  Host transport: synchronise, copy out, reduce, copy back (hv: the
-// pinned mirror of dv).  Timing communicator: skipped.
-int kr_reduce(sss_hip_dist *d, double *dv, double *hv, int n)
-{
-    sss_hip_comm *c = d->comm;
-    if (c->timing) return 0;
-    if (!c->host) {
-        SSS_NCCL(ncclAllReduce(dv, dv, (size_t)n, ncclDouble, ncclSum, c->nccl, d->stream));
+// The row-partitioned engine as the Krylov solvers see it (KrylovEngine, sss_engine.hpp): vectors
+// are this rank's rows; what reads off-rank values goes through the level vectors, which have the
+// halo slots.
+struct DistEngine final : KrylovEngine {
+    sss_hip_dist *d;
+    DLevel &L;
+    explicit DistEngine(sss_hip_dist *dist) : d(dist), L(dist->L[0])
+    {
+        n = L.m;
+        stream = d->stream;
+        b = L.b;
+        x = L.x;
+    }
+    size_t bytes() const { return sizeof(double) * (size_t)n; }
+    // dv[0 .. count) summed over the ranks, in place on the device.  RCCL: enqueued on the engine
+    // stream, nothing comes to the host.  Host transport: synchronise, copy out, reduce, copy back
+    // (hv: the pinned mirror of dv).  Timing communicator: skipped.
+    int reduce(double *dv, double *hv, int count) override
+    {
+        sss_hip_comm *c = d->comm;
+        if (c->timing) return 0;
+        if (!c->host) {
+            SSS_NCCL(ncclAllReduce(dv, dv, (size_t)count, ncclDouble, ncclSum, c->nccl, stream));
+            return 0;
+        }
+        SSS_HIP(hipMemcpyAsync(hv, dv, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, stream));
+        SSS_HIP(hipStreamSynchronize(stream));
+        if (c->t.allreduce_sum(c->t.ctx, hv, count)) return ERROR_MISC;
+        SSS_HIP(hipMemcpyAsync(dv, hv, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream));
         return 0;
     }
-    SSS_HIP(hipMemcpyAsync(hv, dv, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-    SSS_HIP(hipStreamSynchronize(d->stream));
-    if (c->t.allreduce_sum(c->t.ctx, hv, n)) return ERROR_MISC;
-    SSS_HIP(hipMemcpyAsync(dv, hv, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, d->stream));
-    return 0;
-}
-
-// hv[0 .. n) = dv[0 .. n): the iteration's one read-back
-int kr_fetch(sss_hip_dist *d, const double *dv, double *hv, int n)
-{
-    SSS_HIP(hipMemcpyAsync(hv, dv, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-    SSS_HIP(hipStreamSynchronize(d->stream));
-    return 0;
-}
-
-int kr_stalled(sss_hip_dist *d, const char *who)
-{
-    fprintf(stderr, "### ERROR: %s (rank %d): an exact Gauss-Seidel pass stalled on the GPU (spin limit reached); "
-                    "the iterate is invalid\n", who, d->comm->rank);
-    return ERROR_MISC;
-}
-
-// out = A_0 vec over this rank's rows; vec is own rows + ghosts long and its halo is refreshed here
-// (overlapping the interior blocks), as residual() does for x
-int apply_A(sss_hip_dist *d, double *vec, double *out)
-{
-    DLevel &L = d->L[0];
-    if (L.A.wave_rows || L.A.vec_rows) {
-        int rc = exchange(d, 0, vec);
-        return rc ? rc : launch_spmv(L.A, SSS_HIP_SPMV_MXY, 1.0, vec, nullptr, out, 0, nullptr, d->stream);
+    unsigned *stall_word() override { return d->d_err; }
+    int stalled(const char *who) override
+    {
+        fprintf(stderr, "### ERROR: %s (rank %d): an exact Gauss-Seidel pass stalled on the GPU (spin limit reached); "
+                        "the iterate is invalid\n", who, d->comm->rank);
+        return ERROR_MISC;
     }
-    int lrc = 0;
-    const int rc = split_launch(d, 0, vec, L.ghostA, 0, L.A.nblk, [&](int b0, int b1) {
-        lrc = lrc ? lrc : launch_spmv_range(L.A, b0, b1, SSS_HIP_SPMV_MXY, 1.0, vec, nullptr, out, nullptr, d->stream);
-    });
-    return rc ? rc : lrc;
-}
-
-// level-0 x = one cycle on (level-0 b, 0): the preconditioner, its result left in L.x
-int kr_precondition(sss_hip_dist *d)
-{
-    DLevel &L = d->L[0];
-    SSS_HIP(hipMemsetAsync(L.x, 0, sizeof(double) * (size_t)(L.m + L.g), d->stream));
-    return sss_hip_dist_cycle(d);
-}
-
-// hcol[i] = c1[i] + c2[i] for i < k (the Hessenberg column from the reduced coefficients of the two
-// Gram-Schmidt passes), hcol[k] = sqrt(ns[0]) (the norm, root taken after the reduction),
-// hcol[k + 1] = ns[1] (the stall flag, for the same read-back)
-__global__ __launch_bounds__(256) void arnoldi_finish(int k, const double *__restrict__ c1, const double *__restrict__ c2,
-                                                       const double *__restrict__ ns, double *__restrict__ hcol)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < k) hcol[i] = c1[i] + c2[i];
-    else if (i == k) hcol[k] = sqrt(ns[0]);
-    else if (i == k + 1) hcol[k + 1] = ns[1];
-}
+    // out = A_0 vec over this rank's rows; vec is own rows + ghosts long and its halo is refreshed here
+    // (overlapping the interior blocks), as residual() does for x
+    int apply_A(double *vec, double *out)
+    {
+        if (L.A.wave_rows || L.A.vec_rows) {
+            int rc = exchange(d, 0, vec);
+            return rc ? rc : launch_spmv(L.A, SSS_HIP_SPMV_MXY, 1.0, vec, nullptr, out, 0, nullptr, stream);
+        }
+        int lrc = 0;
+        const int rc = split_launch(d, 0, vec, L.ghostA, 0, L.A.nblk, [&](int b0, int b1) {
+            lrc = lrc ? lrc : launch_spmv_range(L.A, b0, b1, SSS_HIP_SPMV_MXY, 1.0, vec, nullptr, out, nullptr, stream);
+        });
+        return rc ? rc : lrc;
+    }
+    // level-0 x = one cycle on (level-0 b, 0): the preconditioner, its result left in L.x
+    int precondition()
+    {
+        SSS_HIP(hipMemsetAsync(L.x, 0, sizeof(double) * (size_t)(L.m + L.g), stream));
+        return sss_hip_dist_cycle(d);
+    }
+    // through the level vectors, whose x carries the halo
+    int residual(const double *xv, const double *bv, double *out) override
+    {
+        SSS_HIP(hipMemcpyAsync(L.b, bv, bytes(), hipMemcpyDeviceToDevice, stream));
+        SSS_HIP(hipMemcpyAsync(L.x, xv, bytes(), hipMemcpyDeviceToDevice, stream));
+        if (int rc = ::residual(d, 0, false, nullptr)) return rc;
+        SSS_HIP(hipMemcpyAsync(out, L.wp, bytes(), hipMemcpyDeviceToDevice, stream));
+        return 0;
+    }
+    int precondition_apply(const double *v, double *z, double *w) override
+    {
+        SSS_HIP(hipMemcpyAsync(L.b, v, bytes(), hipMemcpyDeviceToDevice, stream));
+        if (int rc = precondition()) return rc;
+        SSS_HIP(hipMemcpyAsync(z, L.x, bytes(), hipMemcpyDeviceToDevice, stream));
+        return apply_A(L.x, w);   // w = A z, z read where the cycle left it
+    }
+};
 
 }  // namespace
 
@@ -1056,6 +1050,7 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
     const int m = L.m;
     const size_t ld = (size_t)m + (m & 1), bytes = sizeof(double) * (size_t)m;
     const hipStream_t s = d->stream;
+    DistEngine eng(d);
     if (!d->kr_s) {
         d->kr_part = dev_alloc<double>(2 * kOrthBlocks + kFinalScratch);
         d->kr_s = dev_alloc<double>(8);
@@ -1079,8 +1074,8 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
         int rc;
         SSS_HIP(hipMemcpyAsync(bs, L.b, bytes, hipMemcpyDeviceToDevice, s));
         SSS_HIP(hipMemcpyAsync(xs, L.x, bytes, hipMemcpyDeviceToDevice, s));
-        if ((rc = launch_dot(m, bs, bs, part, S + NB2, s)) || (rc = kr_reduce(d, S + NB2, Hh + NB2, 1)) ||
-            (rc = kr_fetch(d, S + NB2, Hh + NB2, 1)))
+        if ((rc = launch_dot(m, bs, bs, part, S + NB2, s)) || (rc = eng.reduce(S + NB2, Hh + NB2, 1)) ||
+            (rc = eng.fetch(S + NB2, Hh + NB2, 1)))
             return rc;
         const double nb = std::sqrt(Hh[NB2]);   // the global ||b||: the same on every rank
         if (!std::isfinite(nb)) return ERROR_SOLVER_EXIT;
@@ -1093,34 +1088,34 @@ extern "C" int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *ite
         SSS_HIP(hipMemcpyAsync(r, L.wp, bytes, hipMemcpyDeviceToDevice, s));
         // the global ||r_0||^2, one reduction before the loop: zero (x solves the system exactly; z = 0
         // would make the first step length 0 / 0) and non-finite leave here, on every rank alike
-        if ((rc = launch_dot(m, r, r, part, S + RR, s)) || (rc = kr_reduce(d, S + RR, Hh + RR, 1)) ||
-            (rc = kr_fetch(d, S + RR, Hh + RR, 1)))
+        if ((rc = launch_dot(m, r, r, part, S + RR, s)) || (rc = eng.reduce(S + RR, Hh + RR, 1)) ||
+            (rc = eng.fetch(S + RR, Hh + RR, 1)))
             return rc;
         if (!std::isfinite(Hh[RR])) return ERROR_SOLVER_EXIT;
         if (Hh[RR] == 0.0) {
             rel = 0.0;
             return 0;
         }
-        if ((rc = kr_precondition(d))) return rc;
-        if ((rc = launch_dot(m, r, z, part, S + RZ, s)) || (rc = kr_reduce(d, S + RZ, Hh + RZ, 1))) return rc;
+        if ((rc = eng.precondition())) return rc;
+        if ((rc = launch_dot(m, r, z, part, S + RZ, s)) || (rc = eng.reduce(S + RZ, Hh + RZ, 1))) return rc;
         SSS_HIP(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, s));
         for (;;) {
             ++it;
-            if ((rc = apply_A(d, p, q))) return rc;                                                  // q = A p
-            if ((rc = launch_dot(m, p, q, part, S + PQ, s)) || (rc = kr_reduce(d, S + PQ, Hh + PQ, 1))) return rc;
+            if ((rc = eng.apply_A(p, q))) return rc;                                                  // q = A p
+            if ((rc = launch_dot(m, p, q, part, S + PQ, s)) || (rc = eng.reduce(S + PQ, Hh + PQ, 1))) return rc;
             // x += a p, r_old = r, r -= a q, a = rz / pq; r.r and the stall word in one reduction
             if ((rc = launch_pcg_update(m, S + RZ, S + PQ, p, q, xs, r, ro, part, s))) return rc;
             if ((rc = launch_final_sum(part, kOrthBlocks, S + RR, false, s))) return rc;
             if ((rc = launch_err_flag(d->d_err, S + STALL, s))) return rc;
-            if ((rc = kr_reduce(d, S + RR, Hh + RR, 2)) || (rc = kr_fetch(d, S + RR, Hh + RR, 2))) return rc;
-            if (Hh[STALL] != 0.0) return kr_stalled(d, "sss_hip_dist_pcg");
+            if ((rc = eng.reduce(S + RR, Hh + RR, 2)) || (rc = eng.fetch(S + RR, Hh + RR, 2))) return rc;
+            if (Hh[STALL] != 0.0) return eng.stalled("sss_hip_dist_pcg");
             if (!std::isfinite(Hh[RR])) return ERROR_SOLVER_EXIT;
             rel = std::sqrt(Hh[RR]) / nb;
             if (hist && it <= hist_cap) hist[it - 1] = rel;
             if (rel < tol || it >= maxit) return 0;
-            if ((rc = kr_precondition(d))) return rc;
-            if ((rc = launch_dot2(m, r, ro, z, part, s)) || (rc = launch_multi_final(2, part, S + RZN, nullptr, true, s)) ||
-                (rc = kr_reduce(d, S + RZN, Hh + RZN, 2)))
+            if ((rc = eng.precondition())) return rc;
+            if ((rc = launch_dot2(m, r, ro, z, part, s)) || (rc = launch_multi_final(2, part, S + RZN, s)) ||
+                (rc = eng.reduce(S + RZN, Hh + RZN, 2)))
                 return rc;
             if (m > 0 && (rc = launch_xpby_ratio(m, S + RZN, S + ROZ, S + RZ, z, p, s))) return rc;   // p = z + ((r-ro).z / rz) p
             SSS_HIP(hipMemcpyAsync(S + RZ, S + RZN, sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1141,135 +1136,12 @@ extern "C" int sss_hip_dist_fgmres(sss_hip_dist *d, double tol, int restart, int
                                    double *hist, int hist_cap)
 {
     if (!d || restart < 1) return ERROR_INPUT_PAR;   // before any collective: the same on every rank
-    DLevel &L = d->L[0];
-    const int n = L.m;
+    DistEngine eng(d);
     const int m = std::min(restart, std::max(maxit, 1));
-    const size_t ld = (size_t)n + (n & 1);   // every column 16-byte aligned
-    const hipStream_t s = d->stream;
-    if (m > d->fg_m) {
-        SSS_HIP(hipStreamSynchronize(s));
-        fgmres_free(d);
-        const size_t ns = (size_t)4 * m + 4;
-        d->fg_v = dev_alloc<double>(((size_t)2 * m + 3) * ld);
-        d->fg_part = dev_alloc<double>(orth_part_doubles(m));
-        d->fg_s = dev_alloc<double>(ns);
-        if (!d->fg_v || !d->fg_part || !d->fg_s) {
-            fgmres_free(d);
-            return hip_fail(hipErrorOutOfMemory, "hipMalloc(dist fgmres)", __FILE__, __LINE__);
-        }
-        SSS_HIP(hipHostMalloc((void **)&d->fg_h, ns * sizeof(double), hipHostMallocDefault));
-        SSS_HIP(hipMemsetAsync(d->fg_s, 0, ns * sizeof(double), s));
-        d->fg_m = m;
-    }
-    const int cap = d->fg_m;
-    double *V = d->fg_v, *Z = V + ((size_t)cap + 1) * ld, *bs = Z + (size_t)cap * ld, *xs = bs + ld;
-    double *dc1 = d->fg_s, *dc2 = dc1 + cap, *dns = dc2 + cap, *dh = dns + 2, *dy = dh + cap + 2;
-    double *H0 = d->fg_h, *hns = H0 + (dns - dc1), *hh = H0 + (dh - dc1), *yh = H0 + (dy - dc1);
-    double *npart = d->fg_part, *dpart = d->fg_part + kOrthBlocks + kFinalScratch;
-    const size_t bytes = sizeof(double) * (size_t)n;
+    if (int rc = d->fg.ensure(m, (size_t)eng.n + (eng.n & 1), d->stream)) return rc;
     d->resid_c_ready = false;
-    int it = 0;
-    double rel = 1.0;
-    auto finish = [&](int k) -> int {   // dh[0 .. k) = c1 + c2, dh[k] = sqrt of the reduced sum, dh[k + 1] = stall
-        hipLaunchKernelGGL(arnoldi_finish, dim3((k + 2 + 255) / 256), dim3(256), 0, s, k, dc1, dc2, dns, dh);
-        SSS_HIP(hipGetLastError());
-        return 0;
-    };
-    auto norm_of = [&](const double *v, double *out) -> int {   // dh[0] = the global ||v||, also returned
-        int c = launch_multi_dot(n, 1, v, ld, v, dpart, s);
-        if (!c) c = launch_final_sum(dpart, kOrthBlocks, dns, false, s);
-        if (!c) c = kr_reduce(d, dns, hns, 1);
-        if (!c) c = finish(0);
-        if (!c) c = kr_fetch(d, dh, hh, 1);
-        *out = hh[0];
-        return c;
-    };
-    auto solve = [&]() -> int {
-        int rc;
-        SSS_HIP(hipMemcpyAsync(bs, L.b, bytes, hipMemcpyDeviceToDevice, s));
-        SSS_HIP(hipMemcpyAsync(xs, L.x, bytes, hipMemcpyDeviceToDevice, s));
-        double nb = 0.0;
-        std::vector<double> R((size_t)(m + 1) * m, 0.0), cs((size_t)m), sn((size_t)m), g((size_t)m + 1);   // R: column-major
-        if ((rc = norm_of(bs, &nb))) return rc;
-        if (!std::isfinite(nb)) return ERROR_SOLVER_EXIT;
-        if (nb == 0.0) {
-            SSS_HIP(hipMemsetAsync(xs, 0, bytes, s));
-            rel = 0.0;
-            return 0;
-        }
-        bool done = maxit < 1;
-        while (!done) {
-            double beta = 0.0;
-            // r = b - A x: through the level vectors, whose x carries the halo
-            SSS_HIP(hipMemcpyAsync(L.b, bs, bytes, hipMemcpyDeviceToDevice, s));
-            SSS_HIP(hipMemcpyAsync(L.x, xs, bytes, hipMemcpyDeviceToDevice, s));
-            if ((rc = residual(d, 0, false, nullptr))) return rc;
-            SSS_HIP(hipMemcpyAsync(V, L.wp, bytes, hipMemcpyDeviceToDevice, s));
-            if ((rc = norm_of(V, &beta))) return rc;
-            if (!std::isfinite(beta)) return ERROR_SOLVER_EXIT;
-            if (it == 0) rel = beta / nb;
-            if (beta == 0.0) return 0;   // x solves the system exactly
-            if ((rc = launch_scale_inv(n, V, dh, s))) return rc;   // v_0 = r / ||r||
-            g[0] = beta;
-            int ncols = 0;
-            for (int j = 0; j < m && !done; ++j) {
-                ++it;
-                const int k = j + 1;
-                double *w = V + (size_t)(j + 1) * ld, *hj = R.data() + (size_t)j * (m + 1);
-                SSS_HIP(hipMemcpyAsync(L.b, V + (size_t)j * ld, bytes, hipMemcpyDeviceToDevice, s));
-                if ((rc = kr_precondition(d))) return rc;
-                SSS_HIP(hipMemcpyAsync(Z + (size_t)j * ld, L.x, bytes, hipMemcpyDeviceToDevice, s));
-                if ((rc = apply_A(d, L.x, w))) return rc;   // w = A z_j, z_j read where the cycle left it
-                // CGS2 with the three reductions of the step between the fused kernels
-                if ((rc = launch_multi_dot(n, k, V, ld, w, dpart, s)) || (rc = launch_multi_final(k, dpart, dc1, nullptr, true, s)) ||
-                    (rc = kr_reduce(d, dc1, H0, k)) || (rc = launch_multi_axpy(n, k, V, ld, dc1, -1.0, w, nullptr, s)))
-                    return rc;
-                if ((rc = launch_multi_dot(n, k, V, ld, w, dpart, s)) || (rc = launch_multi_final(k, dpart, dc2, nullptr, true, s)) ||
-                    (rc = kr_reduce(d, dc2, H0 + cap, k)) || (rc = launch_multi_axpy(n, k, V, ld, dc2, -1.0, w, npart, s)))
-                    return rc;
-                if ((rc = launch_final_sum(npart, kOrthBlocks, dns, false, s)) || (rc = launch_err_flag(d->d_err, dns + 1, s)) ||
-                    (rc = kr_reduce(d, dns, hns, 2)) || (rc = finish(k)))
-                    return rc;
-                if ((rc = launch_scale_inv(n, w, dh + k, s))) return rc;   // v_{j+1} = w / ||w||
-                if ((rc = kr_fetch(d, dh, hh, k + 2))) return rc;
-                if (hh[k + 1] != 0.0) return kr_stalled(d, "sss_hip_dist_fgmres");
-                if (!std::isfinite(hh[k])) return ERROR_SOLVER_EXIT;
-                for (int i = 0; i < k + 1; ++i) hj[i] = hh[i];
-                for (int i = 0; i < j; ++i) {   // the earlier rotations, then the one that clears h_{j+1,j}
-                    const double t = cs[i] * hj[i] + sn[i] * hj[i + 1];
-                    hj[i + 1] = -sn[i] * hj[i] + cs[i] * hj[i + 1];
-                    hj[i] = t;
-                }
-                const double dd = std::hypot(hj[j], hj[j + 1]);
-                cs[j] = dd != 0.0 ? hj[j] / dd : 1.0;
-                sn[j] = dd != 0.0 ? hj[j + 1] / dd : 0.0;
-                hj[j] = dd;
-                g[j + 1] = -sn[j] * g[j];
-                g[j] = cs[j] * g[j];
-                rel = std::fabs(g[j + 1]) / nb;
-                if (hist && it <= hist_cap) hist[it - 1] = rel;
-                ncols = k;
-                done = rel < tol || it >= maxit || hh[k] == 0.0;
-            }
-            for (int i = ncols - 1; i >= 0; --i) {   // R y = g
-                double t = g[i];
-                for (int l = i + 1; l < ncols; ++l) t -= R[(size_t)l * (m + 1) + i] * yh[l];
-                yh[i] = R[(size_t)i * (m + 1) + i] != 0.0 ? t / R[(size_t)i * (m + 1) + i] : 0.0;
-            }
-            SSS_HIP(hipMemcpyAsync(dy, yh, sizeof(double) * (size_t)ncols, hipMemcpyHostToDevice, s));
-            if ((rc = launch_multi_axpy(n, ncols, Z, ld, dy, 1.0, xs, nullptr, s))) return rc;   // x += Z y
-            SSS_HIP(hipStreamSynchronize(s));   // yh is rewritten at the next restart
-        }
-        return 0;
-    };
-    const int rc = solve();
-    // the caller's b back, and the iterate (after an error: the last one formed)
-    SSS_HIP(hipMemcpyAsync(L.x, xs, bytes, hipMemcpyDeviceToDevice, s));
-    SSS_HIP(hipMemcpyAsync(L.b, bs, bytes, hipMemcpyDeviceToDevice, s));
-    SSS_HIP(hipStreamSynchronize(s));
+    const int rc = fgmres_solve(eng, d->fg, m, tol, maxit, iters, relres, hist, hist_cap, "sss_hip_dist_fgmres");
     d->resid_c_ready = false;
-    if (iters) *iters = it;
-    if (relres) *relres = rel;
     return rc;
 }
 

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstdint>
 #include <cstdlib>
 #include <string>
 #include <functional>
@@ -666,26 +667,78 @@ int launch_xpby_ratio(int n, const double *num, const double *numold, const doub
 int launch_pcg_update(int n, const double *num, const double *den, const double *p, const double *q, double *x,
                       double *r, double *r_old, double *partial, hipStream_t s);
 // partial[0 .. 1024) = partials of r.z, partial[1024 .. 2048) = of r_old.z, in one pass over z (sum
-// them with launch_multi_final(2, partial, out, ...)).
+// them with launch_multi_final(2, partial, out, s)).
 int launch_dot2(int n, const double *r, const double *r_old, const double *z, double *partial, hipStream_t s);
 
 // ---- multi-vector orthogonalisation for the flexible GMRES (sss_fgmres.hip) ------------------
 // V: k columns back to back with leading dimension ld >= n (ld even, V and w 16-byte aligned).
 constexpr int kOrthBlocks = 1024;   // partial sums per dot product (fixed grid, fixed order)
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 // doubles of `part` for a step against up to k columns: the norm's partials, then k dots' partials
 inline size_t orth_part_doubles(int k) { return (size_t)kOrthBlocks * (k + 1) + kFinalScratch; }
 // part[i * kOrthBlocks + b] = workgroup b's share of <w, v_i>, i < k
 int launch_multi_dot(int n, int k, const double *V, size_t ld, const double *w, double *part, hipStream_t s);
-// c[i] = sum of part[i][.]; hcol (optional): hcol[i] = c[i] (first) or hcol[i] + c[i]
-int launch_multi_final(int k, const double *part, double *c, double *hcol, bool first, hipStream_t s);
+// c[i] = sum of part[i][.]
+int launch_multi_final(int k, const double *part, double *c, hipStream_t s);
 // w += sign * sum_i coef[i] v_i (coef on the device); npart (optional): kOrthBlocks partials of ||w||^2
 int launch_multi_axpy(int n, int k, const double *V, size_t ld, const double *coef, double sign, double *w,
                       double *npart, hipStream_t s);
 // w /= *nrm (*nrm on the device; zero leaves w unchanged)
 int launch_scale_inv(int n, double *w, const double *nrm, hipStream_t s);
-// CGS2 of w against V: hcol[0 .. k) = c1 + c2, hcol[k] = ||w||; c: k doubles, part: orth_part_doubles(k)
-int launch_orth_step(int n, int k, const double *V, size_t ld, double *w, double *part, double *c, double *hcol,
-                     hipStream_t s);
+// hcol[i] = c1[i] + c2[i] for i < k, hcol[k] = sqrt(ns[0]), hcol[k + 1] = ns[1]
+int launch_arnoldi_finish(int k, const double *c1, const double *c2, const double *ns, double *hcol, hipStream_t s);
+
+// ---- AMG-preconditioned flexible GMRES: one loop for every engine (sss_fgmres.hip) -----------
+// What the loop asks of an engine.  All vectors are the engine's own rows of level 0; every
+// operation is enqueued on `stream`.
+struct KrylovEngine {
+    int n = 0;                     // own rows
+    hipStream_t stream = nullptr;
+    double *b = nullptr, *x = nullptr;   // the level-0 right-hand side and iterate (own rows)
+    virtual ~KrylovEngine() = default;
+    virtual int residual(const double *x, const double *b, double *out) = 0;   // out = b - A x
+    // z = one cycle on (v, 0), w = A z
+    virtual int precondition_apply(const double *v, double *z, double *w) = 0;
+    // dv[0 .. count) summed over the ranks, in place on the device (hv: its pinned host mirror)
+    virtual int reduce(double *dv, double *hv, int count) { return 0; }
+    // the device stall word the loop folds into its per-iteration read-back (null: the engine looks
+    // at its own after the solve), and the error return when it is set
+    virtual unsigned *stall_word() { return nullptr; }
+    virtual int stalled(const char *who) { return ERROR_MISC; }
+    // hv[0 .. count) = dv[0 .. count), synchronised: an iteration's one read-back
+    int fetch(const double *dv, double *hv, int count)
+    {
+        SSS_HIP(hipMemcpyAsync(hv, dv, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, stream));
+        SSS_HIP(hipStreamSynchronize(stream));
+        return 0;
+    }
+};
+// Workspace of fgmres_solve, kept by the engine's handle and sized for m = the largest restart so far.
+struct FgmresWork {
+    double *v = nullptr;      // 2 m + 3 vectors of ld: V (m + 1), Z (m), saved b, iterate x
+    double *part = nullptr;   // orth_part_doubles(m)
+    double *s = nullptr;      // 4 m + 4 scalars: c1, c2 (m each), {||w||^2, stall}, Hessenberg column + norm + stall, y
+    double *h = nullptr;      // pinned host mirror of s
+    int m = 0;
+    // room for restart m at leading dimension ld (grows only; the scalars start zeroed)
+    int ensure(int m, size_t ld, hipStream_t stream);
+    void release();
+};
+// The scalars of one Arnoldi step: device pointers into a block of which `mirror` is the pinned
+// host copy at the same offsets from c1 (null without a reduction).
+struct OrthScalars {
+    double *c1, *c2, *ns, *hcol;   // k, k, 2, k + 2 doubles
+    double *mirror;
+};
+// CGS2 of w against the k columns of V, the three partial results summed over the ranks by
+// eng->reduce (eng null: one rank, no stall word): hcol[0 .. k) = c1 + c2, hcol[k] = ||w||,
+// hcol[k + 1] = the stall flag (ns[1] where there is no stall word).  part: orth_part_doubles(k).
+int launch_orth_step(int n, int k, const double *V, size_t ld, double *w, double *part, const OrthScalars &sc,
+                     KrylovEngine *eng, hipStream_t s);
+// The solver of sss_hip_fgmres and sss_hip_dist_fgmres from "save b and x" to "restore b and x";
+// m = min(restart, max(maxit, 1)) <= W.m.  `who` names the caller in the stall message.
+int fgmres_solve(KrylovEngine &eng, FgmresWork &W, int m, double tol, int maxit, int *iters, double *relres,
+                 double *hist, int hist_cap, const char *who);
 
 // ---- coarse solvers ------------------------------------------------------------------------
 struct CoarseDirect {

@@ -1,5 +1,6 @@
-// sss_fgmres.hip — fused multi-vector orthogonalisation for the AMG-preconditioned flexible GMRES
-// (sss_hip_fgmres, sss_hier.hip), fp64.
+// sss_fgmres.hip — the AMG-preconditioned flexible GMRES of every engine (sss_hip_fgmres,
+// sss_hip_dist_fgmres): the solver loop fgmres_solve over the KrylovEngine interface of
+// sss_engine.hpp, its workspace, and the fused multi-vector orthogonalisation it runs on, fp64.
 //
 // One Arnoldi step orthogonalises w against the basis V = [v_0 .. v_{k-1}] (columns back to back,
 // leading dimension ld, every column 16-byte aligned) by classical Gram-Schmidt applied twice:
@@ -9,15 +10,17 @@
 //   multi_dot   c[i] = <w, v_i> for all i in one pass: w is read once per kOrthCols columns, the
 //               columns in register blocks of kOrthWidth.  Fixed grid (kOrthBlocks contiguous
 //               chunks), lane-strided sums, xor tree, waves in order -> part[i][block].
-//   multi_final one workgroup per column sums its kOrthBlocks partials in a fixed order; the second
-//               pass adds its coefficients into the Hessenberg column on the device.
+//   multi_final one workgroup per column sums its kOrthBlocks partials in a fixed order.
 //   multi_axpy  w += sign * sum_i c[i] v_i, coefficients from device memory; the same launch leaves
 //               the per-workgroup partials of ||w||^2 of the new w (same chunks, same order).
+//   arnoldi_finish  h = c1 + c2 and the root of ||w||^2, from the coefficients and the sum as the
+//               engine's reduction over the ranks left them (one small workgroup).
 //   scale       w /= *nrm (the next basis vector; the norm stays on the device).
 //
 // No atomics anywhere: results are bitwise reproducible run to run.  All HBM-bound: a step at
-// k columns moves (4k + 6) * 8n bytes in 8 launches (2 x (dot, final, axpy), the norm's final sum,
-// the scale's 16n on top), against (5k) * 8n and 3k launches for a chain of dot + axpy pairs.
+// k columns moves (4k + 6) * 8n bytes in 9 launches (2 x (dot, final, axpy), the norm's final sum,
+// the finish, the scale's 16n on top), against (5k) * 8n and 3k launches for a chain of dot + axpy
+// pairs.  An engine with a stall word adds the one-thread launch that folds it into the read-back.
 #include "sss_engine.hpp"
 #include "sss_spmv_dev.hpp"
 
@@ -32,16 +35,6 @@ constexpr int kOrthWidth = 8;                 // columns per register block
 constexpr int kOrthMaxNB = 3;                 // register blocks one multi_dot launch holds (200 VGPRs, 2 waves/SIMD)
 constexpr int kOrthCols = kOrthWidth * kOrthMaxNB;
 
-// The chunk of workgroup b: [lo, hi), lo even so that the 16-byte loads stay aligned.
-__device__ __forceinline__ void orth_chunk(int n, int &lo, int &hi)
-{
-    int per = (n + kOrthBlocks - 1) / kOrthBlocks;
-    per += per & 1;
-    const long long a = (long long)blockIdx.x * per;
-    lo = a < n ? (int)a : n;
-    hi = a + per < n ? (int)(a + per) : n;
-}
-
 // part[c * kOrthBlocks + block] = sum over the block's chunk of w[i] * v_c[i], c < k <= NB * kOrthWidth.
 // Columns k .. NB * kOrthWidth - 1 of the last register block alias column 0 (loads that hit the
 // cache, results dropped), so every load of an iteration is issued before the first use.
@@ -52,7 +45,7 @@ __global__ __launch_bounds__(kBlock) void multi_dot_partials(int n, int k, const
     constexpr int KC = NB * kOrthWidth;
     __shared__ double red[KC * (kBlock / 64)];
     int lo, hi;
-    orth_chunk(n, lo, hi);
+    dot_chunk(n, lo, hi);
     double acc[KC];
 #pragma unroll
     for (int c = 0; c < KC; ++c) acc[c] = 0.0;
@@ -88,19 +81,15 @@ __global__ __launch_bounds__(kBlock) void multi_dot_partials(int n, int k, const
     }
 }
 
-// c[b] = sum of column b's partials; hcol[b] = c[b] (first pass) or hcol[b] + c[b] (second pass)
-__global__ __launch_bounds__(kBlock) void multi_final(const double *__restrict__ part, double *__restrict__ c,
-                                                      double *__restrict__ hcol, int first)
+// c[b] = sum of column b's partials
+__global__ __launch_bounds__(kBlock) void multi_final(const double *__restrict__ part, double *__restrict__ c)
 {
     __shared__ double red[kBlock / 64];
     const double *p = part + (size_t)blockIdx.x * kOrthBlocks;
     double s = 0.0;
     for (int i = threadIdx.x; i < kOrthBlocks; i += kBlock) s += p[i];
     const double t = block_sum(s, red);
-    if (threadIdx.x == 0) {
-        c[blockIdx.x] = t;
-        if (hcol) hcol[blockIdx.x] = first ? t : hcol[blockIdx.x] + t;
-    }
+    if (threadIdx.x == 0) c[blockIdx.x] = t;
 }
 
 // w[i] += sign * (coef[0] v_0[i] + coef[1] v_1[i] + ...), the sum formed first, in column order;
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_dev(int n, int k, const dou
 {
     __shared__ double red[kBlock / 64];
     int lo, hi;
-    orth_chunk(n, lo, hi);
+    dot_chunk(n, lo, hi);
     double nrm = 0.0;
     for (int i = lo + 2 * (int)threadIdx.x; i < hi; i += 2 * kBlock) {
         if (i + 1 < hi) {
@@ -160,7 +149,17 @@ __global__ __launch_bounds__(kBlock) void scale_inv_dev(int n, double *__restric
     }
 }
 
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// hcol[i] = c1[i] + c2[i] for i < k (the Hessenberg column from the reduced coefficients of the two
+// Gram-Schmidt passes), hcol[k] = sqrt(ns[0]) (the norm, root taken after the reduction),
+// hcol[k + 1] = ns[1] (the stall flag, for the same read-back)
+__global__ __launch_bounds__(256) void arnoldi_finish(int k, const double *__restrict__ c1, const double *__restrict__ c2,
+                                                       const double *__restrict__ ns, double *__restrict__ hcol)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < k) hcol[i] = c1[i] + c2[i];
+    else if (i == k) hcol[k] = sqrt(ns[0]);
+    else if (i == k + 1) hcol[k + 1] = ns[1];
+}
 
 int launch_multi_dot(int n, int k, const double *V, size_t ld, const double *w, double *part, hipStream_t s)
 {
@@ -181,10 +180,10 @@ int launch_multi_dot(int n, int k, const double *V, size_t ld, const double *w, 
     return 0;
 }
 
-int launch_multi_final(int k, const double *part, double *c, double *hcol, bool first, hipStream_t s)
+int launch_multi_final(int k, const double *part, double *c, hipStream_t s)
 {
     if (k < 1) return ERROR_INPUT_PAR;
-    hipLaunchKernelGGL(multi_final, dim3(k), dim3(kBlock), 0, s, part, c, hcol, first ? 1 : 0);
+    hipLaunchKernelGGL(multi_final, dim3(k), dim3(kBlock), 0, s, part, c);
     SSS_HIP(hipGetLastError());
     return 0;
 }
@@ -210,20 +209,165 @@ int launch_scale_inv(int n, double *w, const double *nrm, hipStream_t s)
     return 0;
 }
 
-// One orthogonalisation step (CGS2) of w against the k columns of V.  hcol gets the k Hessenberg
-// coefficients and, in hcol[k], ||w|| of the orthogonalised w; c: k doubles of scratch; part:
-// orth_part_doubles(k) doubles.  Everything stays on the device.
-int launch_orth_step(int n, int k, const double *V, size_t ld, double *w, double *part, double *c, double *hcol,
-                     hipStream_t s)
+int launch_arnoldi_finish(int k, const double *c1, const double *c2, const double *ns, double *hcol, hipStream_t s)
+{
+    if (k < 0) return ERROR_INPUT_PAR;
+    hipLaunchKernelGGL(arnoldi_finish, dim3((k + 2 + 255) / 256), dim3(256), 0, s, k, c1, c2, ns, hcol);
+    SSS_HIP(hipGetLastError());
+    return 0;
+}
+
+// One orthogonalisation step (CGS2) of w against the k columns of V, the same for every engine:
+// each of the three partial results -- c1, c2, {||w||^2, stall flag} -- goes through the engine's
+// reduction over the ranks before it is used.  Everything stays on the device.
+int launch_orth_step(int n, int k, const double *V, size_t ld, double *w, double *part, const OrthScalars &sc,
+                     KrylovEngine *eng, hipStream_t s)
 {
     double *npart = part, *dpart = part + kOrthBlocks + kFinalScratch;
+    auto reduce = [&](double *dv, int count) { return eng ? eng->reduce(dv, sc.mirror + (dv - sc.c1), count) : 0; };
     int rc;
     for (int pass = 0; pass < 2; ++pass) {
-        if ((rc = launch_multi_dot(n, k, V, ld, w, dpart, s))) return rc;
-        if ((rc = launch_multi_final(k, dpart, c, hcol, pass == 0, s))) return rc;
-        if ((rc = launch_multi_axpy(n, k, V, ld, c, -1.0, w, pass ? npart : nullptr, s))) return rc;
+        double *c = pass ? sc.c2 : sc.c1;
+        if ((rc = launch_multi_dot(n, k, V, ld, w, dpart, s)) || (rc = launch_multi_final(k, dpart, c, s)) ||
+            (rc = reduce(c, k)) || (rc = launch_multi_axpy(n, k, V, ld, c, -1.0, w, pass ? npart : nullptr, s)))
+            return rc;
     }
-    return launch_final_sum(npart, kOrthBlocks, hcol + k, true, s);
+    if ((rc = launch_final_sum(npart, kOrthBlocks, sc.ns, false, s))) return rc;
+    unsigned *stall = eng ? eng->stall_word() : nullptr;
+    if (stall && (rc = launch_err_flag(stall, sc.ns + 1, s))) return rc;
+    if ((rc = reduce(sc.ns, 2))) return rc;
+    return launch_arnoldi_finish(k, sc.c1, sc.c2, sc.ns, sc.hcol, s);
+}
+
+void FgmresWork::release()
+{
+    dev_free(v);
+    dev_free(part);
+    dev_free(s);
+    if (h) (void)hipHostFree(h);
+    v = part = s = h = nullptr;
+    m = 0;
+}
+
+int FgmresWork::ensure(int want, size_t ld, hipStream_t stream)
+{
+    if (want <= m) return 0;
+    SSS_HIP(hipStreamSynchronize(stream));
+    release();
+    const size_t ns = (size_t)4 * want + 4;
+    v = dev_alloc<double>(((size_t)2 * want + 3) * ld);
+    part = dev_alloc<double>(orth_part_doubles(want));
+    s = dev_alloc<double>(ns);
+    if (!v || !part || !s) {
+        release();
+        return hip_fail(hipErrorOutOfMemory, "hipMalloc(fgmres)", __FILE__, __LINE__);
+    }
+    SSS_HIP(hipHostMalloc((void **)&h, ns * sizeof(double), hipHostMallocDefault));
+    SSS_HIP(hipMemsetAsync(s, 0, ns * sizeof(double), stream));   // an engine without a stall word never writes its slot
+    m = want;
+    return 0;
+}
+
+// Right-preconditioned FGMRES(m): z_j = one cycle on (v_j, 0), w = A z_j, w orthogonalised against
+// v_0 .. v_j by launch_orth_step, which leaves the Hessenberg column, ||w|| and the stall flag on the
+// device; one read-back of j + 3 doubles per iteration.  Givens rotations and the triangular solve
+// run on the host; x += Z y at a restart, at convergence of the estimate |g_{j+1}| / ||b|| and at
+// maxit.  Every branch and loop exit is taken from reduced values only, so all ranks of a
+// partitioned engine leave in the same iteration.
+int fgmres_solve(KrylovEngine &eng, FgmresWork &W, int m, double tol, int maxit, int *iters, double *relres,
+                 double *hist, int hist_cap, const char *who)
+{
+    const int n = eng.n, cap = W.m;
+    const size_t ld = (size_t)n + (n & 1);   // every column 16-byte aligned
+    const hipStream_t s = eng.stream;
+    double *V = W.v, *Z = V + ((size_t)cap + 1) * ld, *bs = Z + (size_t)cap * ld, *xs = bs + ld;
+    double *dc1 = W.s, *dc2 = dc1 + cap, *dns = dc2 + cap, *dh = dns + 2, *dy = dh + cap + 2;
+    double *H0 = W.h, *hns = H0 + (dns - dc1), *hh = H0 + (dh - dc1), *yh = H0 + (dy - dc1);
+    double *dpart = W.part + kOrthBlocks + kFinalScratch;
+    const OrthScalars sc{dc1, dc2, dns, dh, H0};
+    const size_t bytes = sizeof(double) * (size_t)n;
+    int it = 0;
+    double rel = 1.0;
+    auto norm_of = [&](const double *v, double *out) -> int {   // dh[0] = the global ||v||, also returned
+        int c = launch_multi_dot(n, 1, v, ld, v, dpart, s);
+        if (!c) c = launch_final_sum(dpart, kOrthBlocks, dns, false, s);
+        if (!c) c = eng.reduce(dns, hns, 1);
+        if (!c) c = launch_arnoldi_finish(0, dc1, dc2, dns, dh, s);
+        if (!c) c = eng.fetch(dh, hh, 1);
+        *out = hh[0];
+        return c;
+    };
+    auto solve = [&]() -> int {
+        int rc;
+        SSS_HIP(hipMemcpyAsync(bs, eng.b, bytes, hipMemcpyDeviceToDevice, s));
+        SSS_HIP(hipMemcpyAsync(xs, eng.x, bytes, hipMemcpyDeviceToDevice, s));
+        double nb = 0.0;
+        std::vector<double> R((size_t)(m + 1) * m, 0.0), cs((size_t)m), sn((size_t)m), g((size_t)m + 1);   // R: column-major
+        if ((rc = norm_of(bs, &nb))) return rc;
+        if (!std::isfinite(nb)) return ERROR_SOLVER_EXIT;
+        if (nb == 0.0) {
+            SSS_HIP(hipMemsetAsync(xs, 0, bytes, s));
+            rel = 0.0;
+            return 0;
+        }
+        bool done = maxit < 1;
+        while (!done) {
+            double beta = 0.0;
+            if ((rc = eng.residual(xs, bs, V))) return rc;   // r = b - A x
+            if ((rc = norm_of(V, &beta))) return rc;
+            if (!std::isfinite(beta)) return ERROR_SOLVER_EXIT;
+            if (it == 0) rel = beta / nb;
+            if (beta == 0.0) return 0;   // x solves the system exactly
+            if ((rc = launch_scale_inv(n, V, dh, s))) return rc;   // v_0 = r / ||r||
+            g[0] = beta;
+            int ncols = 0;
+            for (int j = 0; j < m && !done; ++j) {
+                ++it;
+                const int k = j + 1;
+                double *w = V + (size_t)(j + 1) * ld, *hj = R.data() + (size_t)j * (m + 1);
+                if ((rc = eng.precondition_apply(V + (size_t)j * ld, Z + (size_t)j * ld, w))) return rc;
+                if ((rc = launch_orth_step(n, k, V, ld, w, W.part, sc, &eng, s))) return rc;
+                if ((rc = launch_scale_inv(n, w, dh + k, s))) return rc;   // v_{j+1} = w / ||w||
+                if ((rc = eng.fetch(dh, hh, k + 2))) return rc;
+                if (hh[k + 1] != 0.0) return eng.stalled(who);
+                if (!std::isfinite(hh[k])) return ERROR_SOLVER_EXIT;
+                for (int i = 0; i < k + 1; ++i) hj[i] = hh[i];
+                for (int i = 0; i < j; ++i) {   // the earlier rotations, then the one that clears h_{j+1,j}
+                    const double t = cs[i] * hj[i] + sn[i] * hj[i + 1];
+                    hj[i + 1] = -sn[i] * hj[i] + cs[i] * hj[i + 1];
+                    hj[i] = t;
+                }
+                const double d = std::hypot(hj[j], hj[j + 1]);
+                cs[j] = d != 0.0 ? hj[j] / d : 1.0;
+                sn[j] = d != 0.0 ? hj[j + 1] / d : 0.0;
+                hj[j] = d;
+                g[j + 1] = -sn[j] * g[j];
+                g[j] = cs[j] * g[j];
+                rel = std::fabs(g[j + 1]) / nb;
+                if (hist && it <= hist_cap) hist[it - 1] = rel;
+                ncols = k;
+                // h_{j+1,j} = 0 (happy breakdown) gives g_{j+1} = 0: solved with the columns so far
+                done = rel < tol || it >= maxit || hh[k] == 0.0;
+            }
+            for (int i = ncols - 1; i >= 0; --i) {   // R y = g
+                double t = g[i];
+                for (int l = i + 1; l < ncols; ++l) t -= R[(size_t)l * (m + 1) + i] * yh[l];
+                yh[i] = R[(size_t)i * (m + 1) + i] != 0.0 ? t / R[(size_t)i * (m + 1) + i] : 0.0;
+            }
+            SSS_HIP(hipMemcpyAsync(dy, yh, sizeof(double) * (size_t)ncols, hipMemcpyHostToDevice, s));
+            if ((rc = launch_multi_axpy(n, ncols, Z, ld, dy, 1.0, xs, nullptr, s))) return rc;   // x += Z y
+            SSS_HIP(hipStreamSynchronize(s));   // yh is rewritten at the next restart
+        }
+        return 0;
+    };
+    const int rc = solve();
+    // the caller's b back, and the iterate (after an error: the last one formed)
+    SSS_HIP(hipMemcpyAsync(eng.x, xs, bytes, hipMemcpyDeviceToDevice, s));
+    SSS_HIP(hipMemcpyAsync(eng.b, bs, bytes, hipMemcpyDeviceToDevice, s));
+    SSS_HIP(hipStreamSynchronize(s));
+    if (iters) *iters = it;
+    if (relres) *relres = rel;
+    return rc;
 }
 
 }  // namespace sss
@@ -238,16 +382,18 @@ extern "C" int sss_hip_host_orth(int n, int k, const double *V, double *w, doubl
     if (sss_hip_device_count() <= 0) return ERROR_MISC;
     const size_t ld = (size_t)n + (n & 1);
     double *dV = dev_alloc<double>(ld * k), *dw = dev_alloc<double>(ld), *part = dev_alloc<double>(orth_part_doubles(k));
-    double *sc = dev_alloc<double>((size_t)2 * k + 1);
+    double *sc = dev_alloc<double>((size_t)3 * k + 4);   // c1, c2, {||w||^2, stall slot}, column + norm + stall
+    const OrthScalars os{sc, sc + k, sc + 2 * k, sc + 2 * k + 2, nullptr};
     int rc = (!dV || !dw || !part || !sc) ? ERROR_ALLOC_MEM : 0;
+    if (!rc && hipMemset(sc, 0, sizeof(double) * ((size_t)3 * k + 4)) != hipSuccess) rc = ERROR_MISC;
     if (!rc && hipMemcpy2D(dV, ld * sizeof(double), V, (size_t)n * sizeof(double), (size_t)n * sizeof(double), k,
                            hipMemcpyHostToDevice) != hipSuccess)
         rc = ERROR_MISC;
     if (!rc && hipMemcpy(dw, w, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) rc = ERROR_MISC;
-    if (!rc) rc = launch_orth_step(n, k, dV, ld, dw, part, sc, sc + k, nullptr);
+    if (!rc) rc = launch_orth_step(n, k, dV, ld, dw, part, os, nullptr, nullptr);
     if (!rc && hipMemcpy(w, dw, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
-    if (!rc && hipMemcpy(hcol, sc + k, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
-    if (!rc && hipMemcpy(norm, sc + 2 * k, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
+    if (!rc && hipMemcpy(hcol, os.hcol, sizeof(double) * k, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
+    if (!rc && hipMemcpy(norm, os.hcol + k, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
     dev_free(dV);
     dev_free(dw);
     dev_free(part);
@@ -266,9 +412,11 @@ extern "C" int sss_lab_time_orth(int n, int j, int reps, double *fused_ms, doubl
     const int k = j + 1;
     const size_t ld = (size_t)n + (n & 1);
     double *dV = dev_alloc<double>(ld * k), *dw = dev_alloc<double>(ld), *part = dev_alloc<double>(orth_part_doubles(k));
-    double *sc = dev_alloc<double>((size_t)2 * k + 3);
+    double *sc = dev_alloc<double>((size_t)3 * k + 6);   // as sss_hip_host_orth, then the chain's two scalars
+    const OrthScalars os{sc, sc + k, sc + 2 * k, sc + 2 * k + 2, nullptr};
     std::vector<double> col((size_t)n);
     int rc = (!dV || !dw || !part || !sc) ? ERROR_ALLOC_MEM : 0;
+    if (!rc && hipMemset(sc, 0, sizeof(double) * ((size_t)3 * k + 6)) != hipSuccess) rc = ERROR_MISC;
     // columns of magnitude n^-1/2 with a per-column pattern (the time does not depend on the values)
     const double a = 1.0 / std::sqrt((double)n);
     for (int c = 0; c <= k && !rc; ++c) {
@@ -277,7 +425,7 @@ extern "C" int sss_lab_time_orth(int n, int j, int reps, double *fused_ms, doubl
         if (hipMemcpy(dst, col.data(), sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) rc = ERROR_MISC;
     }
     const double one = 1.0;
-    double *d_one = sc + 2 * k + 1, *d_dot = sc + 2 * k + 2;
+    double *d_one = sc + 3 * k + 4, *d_dot = sc + 3 * k + 5;
     if (!rc && hipMemcpy(d_one, &one, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = ERROR_MISC;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = ERROR_MISC;
@@ -286,7 +434,7 @@ extern "C" int sss_lab_time_orth(int n, int j, int reps, double *fused_ms, doubl
         for (int which = 0; which < 2 && !rc; ++which) {
             if (hipEventRecord(e0, nullptr) != hipSuccess) rc = ERROR_MISC;
             if (which == 0) {
-                if (!rc) rc = launch_orth_step(n, k, dV, ld, dw, part, sc, sc + k, nullptr);
+                if (!rc) rc = launch_orth_step(n, k, dV, ld, dw, part, os, nullptr, nullptr);
             } else {
                 for (int c = 0; c < k && !rc; ++c) {
                     rc = launch_dot(n, dw, dV + (size_t)c * ld, part, d_dot, nullptr);

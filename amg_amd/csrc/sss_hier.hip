@@ -81,12 +81,7 @@ struct sss_hip_hier {
     double *pcg_part = nullptr;
     double *pcg_s = nullptr;     // device scalars
     double *pcg_h = nullptr;     // pinned host mirror
-    // AMG-preconditioned flexible GMRES (sss_hip_fgmres), sized for fg_m = the largest restart so far
-    double *fg_v = nullptr;      // 2 fg_m + 3 vectors of ld0: V (fg_m + 1), Z (fg_m), b, x
-    double *fg_part = nullptr;   // orth_part_doubles(fg_m)
-    double *fg_s = nullptr;      // device scalars: c (fg_m), Hessenberg column + norm (fg_m + 1), y (fg_m)
-    double *fg_h = nullptr;      // pinned host mirror of the column + norm and of y
-    int fg_m = 0;
+    FgmresWork fg;               // AMG-preconditioned flexible GMRES (sss_hip_fgmres)
     TailPlan tail;               // the small coarse levels as one single-workgroup launch (sss_tail.hip)
     // per-level timing of an eager cycle (sss_hip_time_levels): an event after each step of the
     // walk, tagged with the level the step belonged to
@@ -235,16 +230,6 @@ static bool natural_level(const sss_hip_hier *h, int gl)
     return h->pars.cf_order == 0 && h->pars.smoother == SSS_SM_GS && hier_kind(h, gl) == SSS_HIP_SMOOTH_EXACT;
 }
 
-static void fgmres_free(sss_hip_hier *h)
-{
-    dev_free(h->fg_v);
-    dev_free(h->fg_part);
-    dev_free(h->fg_s);
-    if (h->fg_h) (void)hipHostFree(h->fg_h);
-    h->fg_v = h->fg_part = h->fg_s = h->fg_h = nullptr;
-    h->fg_m = 0;
-}
-
 static void hier_release(sss_hip_hier *h)
 {
     if (!h) return;
@@ -273,7 +258,7 @@ static void hier_release(sss_hip_hier *h)
     dev_free(h->pcg_part);
     dev_free(h->pcg_s);
     if (h->pcg_h) (void)hipHostFree(h->pcg_h);
-    fgmres_free(h);
+    h->fg.release();
     coarse_direct_free(h->direct);
     coarse_krylov_destroy(h->krylov);
     dev_free(h->partial);
@@ -1242,6 +1227,41 @@ extern "C" int sss_hip_residual_norm(sss_hip_hier *h, double *absres)
     return 0;
 }
 
+// The single-GPU engine as the Krylov solvers see it (KrylovEngine, sss_engine.hpp): every vector
+// is a whole level-0 vector, nothing is summed over ranks, and the stall word is looked at after the
+// solve (hier_stall_check), not inside the iteration.
+namespace {
+struct HierEngine final : KrylovEngine {
+    sss_hip_hier *h;
+    explicit HierEngine(sss_hip_hier *hier) : h(hier)
+    {
+        n = h->L[0].A.n;
+        stream = h->stream;
+        b = h->L[0].b;
+        x = h->L[0].x;
+    }
+    int precondition(const double *v, double *z)   // z = one V-cycle on (v, 0)
+    {
+        const size_t bytes = sizeof(double) * (size_t)n;
+        SSS_HIP(hipMemcpyAsync(b, v, bytes, hipMemcpyDeviceToDevice, stream));
+        SSS_HIP(hipMemsetAsync(x, 0, bytes, stream));
+        int c = sss_hip_cycle(h);
+        if (c) return c;
+        SSS_HIP(hipMemcpyAsync(z, x, bytes, hipMemcpyDeviceToDevice, stream));
+        return 0;
+    }
+    int residual(const double *xv, const double *bv, double *out) override
+    {
+        return launch_spmv(h->L[0].A, SSS_HIP_SPMV_RESID, -1.0, xv, bv, out, 0, nullptr, stream);
+    }
+    int precondition_apply(const double *v, double *z, double *w) override
+    {
+        const int c = precondition(v, z);
+        return c ? c : launch_spmv(h->L[0].A, SSS_HIP_SPMV_MXY, 1.0, z, nullptr, w, 0, nullptr, stream);
+    }
+};
+}  // namespace
+
 // AMG as a preconditioner (not in the reference, whose CG/GMRES serve only
 // the coarsest level): flexible CG with Polak-Ribiere beta, one V-cycle of this hierarchy (its
 // configured smoothers and coarse solve) per iteration as M^-1.  Right-hand side L0.b, initial
@@ -1269,19 +1289,11 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
     double *rz = h->pcg_s, *pq = h->pcg_s + 1, *rr = h->pcg_s + 2, *rzn = h->pcg_s + 3, *roz = h->pcg_s + 4;
     const size_t bytes = sizeof(double) * (size_t)n;
     int rc;
-    auto precondition = [&](const double *rin, double *zout) -> int {   // zout = one V-cycle on (rin, 0)
-        SSS_HIP(hipMemcpyAsync(L.b, rin, bytes, hipMemcpyDeviceToDevice, s));
-        SSS_HIP(hipMemsetAsync(L.x, 0, bytes, s));
-        int c = sss_hip_cycle(h);
-        if (c) return c;
-        SSS_HIP(hipMemcpyAsync(zout, L.x, bytes, hipMemcpyDeviceToDevice, s));
-        return 0;
-    };
+    HierEngine eng(h);
     auto fetch = [&](const double *dv, double *out) -> int {
-        SSS_HIP(hipMemcpyAsync(h->pcg_h, dv, sizeof(double), hipMemcpyDeviceToHost, s));
-        SSS_HIP(hipStreamSynchronize(s));
+        const int c = eng.fetch(dv, h->pcg_h, 1);
         *out = h->pcg_h[0];
-        return 0;
+        return c;
     };
     SSS_HIP(hipMemcpyAsync(bs, L.b, bytes, hipMemcpyDeviceToDevice, s));
     SSS_HIP(hipMemcpyAsync(xs, L.x, bytes, hipMemcpyDeviceToDevice, s));
@@ -1302,7 +1314,7 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
             rel = 0.0;
             return 0;
         }
-        if ((rc = precondition(r, z))) return rc;
+        if ((rc = eng.precondition(r, z))) return rc;
         if ((rc = launch_dot(n, r, z, h->pcg_part, rz, s))) return rc;
         SSS_HIP(hipMemcpyAsync(p, z, bytes, hipMemcpyDeviceToDevice, s));
         while (it < maxit) {
@@ -1317,7 +1329,7 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
             rel = std::sqrt(rr_h) / nb;
             if (hist && it <= hist_cap) hist[it - 1] = rel;
             if (rel < tol) break;
-            if ((rc = precondition(r, z))) return rc;
+            if ((rc = eng.precondition(r, z))) return rc;
             if ((rc = launch_dot(n, r, z, h->pcg_part, rzn, s))) return rc;
             if ((rc = launch_dot(n, ro, z, h->pcg_part, roz, s))) return rc;
             if ((rc = launch_xpby_ratio(n, rzn, roz, rz, z, p, s))) return rc;   // p = z + ((r-ro).z / rz) p
@@ -1337,134 +1349,20 @@ extern "C" int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, d
     return hier_stall_check(h);
 }
 
-// AMG-preconditioned flexible GMRES(restart) for nonsymmetric operators, right-preconditioned: z_j =
-// one V-cycle on (v_j, 0) as in sss_hip_pcg, w = A z_j, and w orthogonalised against v_0 .. v_j by
-// the fused CGS2 step of sss_fgmres.hip, which leaves the Hessenberg column and ||w|| on the device;
-// one read-back of j + 2 doubles per iteration.  Givens rotations and the triangular solve run on
-// the host; x += Z y at a restart, at convergence of the estimate |g_{j+1}| / ||b|| and at maxit.
+// AMG-preconditioned flexible GMRES(restart) for nonsymmetric operators: fgmres_solve
+// (sss_fgmres.hip) on this engine -- z_j = one V-cycle on (v_j, 0) as in sss_hip_pcg, w = A z_j.
 // Right-hand side L0.b (restored on return), initial guess and result L0.x.
 extern "C" int sss_hip_fgmres(sss_hip_hier *h, double tol, int restart, int maxit, int *iters, double *relres,
                               double *hist, int hist_cap)
 {
     if (!h || restart < 1) return ERROR_INPUT_PAR;
-    auto &L = h->L[0];
-    const int n = L.A.n;
+    HierEngine eng(h);
     const int m = std::min(restart, std::max(maxit, 1));
-    const size_t ld = (size_t)n + (n & 1);   // every column 16-byte aligned
-    hipStream_t s = h->stream;
-    if (m > h->fg_m) {
-        SSS_HIP(hipStreamSynchronize(s));
-        fgmres_free(h);
-        h->fg_v = dev_alloc<double>(((size_t)2 * m + 3) * ld);
-        h->fg_part = dev_alloc<double>(orth_part_doubles(m));
-        h->fg_s = dev_alloc<double>((size_t)3 * m + 1);
-        if (!h->fg_v || !h->fg_part || !h->fg_s) {
-            fgmres_free(h);
-            return hip_fail(hipErrorOutOfMemory, "hipMalloc(fgmres)", __FILE__, __LINE__);
-        }
-        SSS_HIP(hipHostMalloc((void **)&h->fg_h, ((size_t)2 * m + 1) * sizeof(double), hipHostMallocDefault));
-        h->fg_m = m;
-    }
-    h->pending_f = false;   // b and x are rewritten below
-    const int cap = h->fg_m;
-    double *V = h->fg_v, *Z = V + ((size_t)cap + 1) * ld, *bs = Z + (size_t)cap * ld, *xs = bs + ld;
-    double *dc = h->fg_s, *dh = dc + cap, *dy = dh + cap + 1;   // dh[k] doubles as the scalar ||.||
-    double *hh = h->fg_h, *yh = hh + cap + 1;
-    const size_t bytes = sizeof(double) * (size_t)n;
-    int rc = 0;
-    auto precondition = [&](const double *rin, double *zout) -> int {   // zout = one V-cycle on (rin, 0)
-        SSS_HIP(hipMemcpyAsync(L.b, rin, bytes, hipMemcpyDeviceToDevice, s));
-        SSS_HIP(hipMemsetAsync(L.x, 0, bytes, s));
-        int c = sss_hip_cycle(h);
-        if (c) return c;
-        SSS_HIP(hipMemcpyAsync(zout, L.x, bytes, hipMemcpyDeviceToDevice, s));
-        return 0;
-    };
-    auto fetch = [&](const double *dv, int cnt) -> int {   // hh[0 .. cnt) = dv[0 .. cnt)
-        SSS_HIP(hipMemcpyAsync(hh, dv, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, s));
-        SSS_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-    auto norm_of = [&](const double *v, double *out) -> int {   // dh[0] = ||v||, also returned
-        int c = launch_multi_dot(n, 1, v, ld, v, h->fg_part + kOrthBlocks + kFinalScratch, s);
-        if (!c) c = launch_final_sum(h->fg_part + kOrthBlocks + kFinalScratch, kOrthBlocks, dh, true, s);
-        if (!c) c = fetch(dh, 1);
-        *out = hh[0];
-        return c;
-    };
-    SSS_HIP(hipMemcpyAsync(bs, L.b, bytes, hipMemcpyDeviceToDevice, s));
-    SSS_HIP(hipMemcpyAsync(xs, L.x, bytes, hipMemcpyDeviceToDevice, s));
-    double nb = 0.0, rel = 1.0;
-    int it = 0;
-    std::vector<double> R((size_t)(m + 1) * m, 0.0), cs((size_t)m), sn((size_t)m), g((size_t)m + 1);   // R: column-major
-    if ((rc = norm_of(bs, &nb))) return rc;
-    if (!std::isfinite(nb)) rc = ERROR_SOLVER_EXIT;
-    if (!rc && nb == 0.0) {
-        SSS_HIP(hipMemsetAsync(xs, 0, bytes, s));
-        rel = 0.0;
-    }
-    bool done = rc || nb == 0.0 || maxit < 1;
-    while (!done) {
-        double beta = 0.0;
-        if ((rc = launch_spmv(L.A, SSS_HIP_SPMV_RESID, -1.0, xs, bs, V, 0, nullptr, s))) break;   // r = b - A x
-        if ((rc = norm_of(V, &beta))) break;
-        if (!std::isfinite(beta)) {
-            rc = ERROR_SOLVER_EXIT;
-            break;
-        }
-        if (it == 0) rel = beta / nb;
-        if (beta == 0.0) break;   // x solves the system exactly
-        if ((rc = launch_scale_inv(n, V, dh, s))) break;   // v_0 = r / ||r||
-        g[0] = beta;
-        int ncols = 0;
-        for (int j = 0; j < m && !done; ++j) {
-            ++it;
-            double *w = V + (size_t)(j + 1) * ld, *hj = R.data() + (size_t)j * (m + 1);
-            if ((rc = precondition(V + (size_t)j * ld, Z + (size_t)j * ld))) break;
-            if ((rc = launch_spmv(L.A, SSS_HIP_SPMV_MXY, 1.0, Z + (size_t)j * ld, nullptr, w, 0, nullptr, s))) break;
-            if ((rc = launch_orth_step(n, j + 1, V, ld, w, h->fg_part, dc, dh, s))) break;
-            if ((rc = launch_scale_inv(n, w, dh + j + 1, s))) break;   // v_{j+1} = w / ||w||
-            if ((rc = fetch(dh, j + 2))) break;
-            if (!std::isfinite(hh[j + 1])) {
-                rc = ERROR_SOLVER_EXIT;
-                break;
-            }
-            for (int i = 0; i < j + 2; ++i) hj[i] = hh[i];
-            for (int i = 0; i < j; ++i) {   // the earlier rotations, then the one that clears h_{j+1,j}
-                const double t = cs[i] * hj[i] + sn[i] * hj[i + 1];
-                hj[i + 1] = -sn[i] * hj[i] + cs[i] * hj[i + 1];
-                hj[i] = t;
-            }
-            const double d = std::hypot(hj[j], hj[j + 1]);
-            cs[j] = d != 0.0 ? hj[j] / d : 1.0;
-            sn[j] = d != 0.0 ? hj[j + 1] / d : 0.0;
-            hj[j] = d;
-            g[j + 1] = -sn[j] * g[j];
-            g[j] = cs[j] * g[j];
-            rel = std::fabs(g[j + 1]) / nb;
-            if (hist && it <= hist_cap) hist[it - 1] = rel;
-            ncols = j + 1;
-            // h_{j+1,j} = 0 (happy breakdown) gives g_{j+1} = 0: solved with the columns so far
-            done = rel < tol || it >= maxit || hh[j + 1] == 0.0;
-        }
-        if (rc) break;
-        for (int i = ncols - 1; i >= 0; --i) {   // R y = g
-            double t = g[i];
-            for (int l = i + 1; l < ncols; ++l) t -= R[(size_t)l * (m + 1) + i] * yh[l];
-            yh[i] = R[(size_t)i * (m + 1) + i] != 0.0 ? t / R[(size_t)i * (m + 1) + i] : 0.0;
-        }
-        SSS_HIP(hipMemcpyAsync(dy, yh, sizeof(double) * (size_t)ncols, hipMemcpyHostToDevice, s));
-        if ((rc = launch_multi_axpy(n, ncols, Z, ld, dy, 1.0, xs, nullptr, s))) break;   // x += Z y
-        SSS_HIP(hipStreamSynchronize(s));   // yh is rewritten at the next restart
-    }
-    // the caller's b back, and the iterate (after an error: the last one formed)
-    SSS_HIP(hipMemcpyAsync(L.x, xs, bytes, hipMemcpyDeviceToDevice, s));
-    SSS_HIP(hipMemcpyAsync(L.b, bs, bytes, hipMemcpyDeviceToDevice, s));
-    SSS_HIP(hipStreamSynchronize(s));
+    if (int rc = h->fg.ensure(m, (size_t)eng.n + (eng.n & 1), h->stream)) return rc;
+    h->pending_f = false;   // b and x are rewritten by the solve
+    const int rc = fgmres_solve(eng, h->fg, m, tol, maxit, iters, relres, hist, hist_cap, "sss_hip_fgmres");
     h->resid_c_ready = false;
     h->pending_f = false;
-    if (iters) *iters = it;
-    if (relres) *relres = rel;
     if (rc) return rc;
     return hier_stall_check(h);
 }

@@ -484,6 +484,17 @@ __device__ __forceinline__ double block_sum(double v, double *red)
     return t;
 }
 
+// The chunk of workgroup b of a fixed grid of kOrthBlocks (the fused BLAS-1 and orthogonalisation
+// kernels): [lo, hi), lo even so that 16-byte accesses stay aligned.
+__device__ __forceinline__ void dot_chunk(int n, int &lo, int &hi)
+{
+    int per = (n + kOrthBlocks - 1) / kOrthBlocks;
+    per += per & 1;
+    const long long a = (long long)blockIdx.x * per;
+    lo = a < n ? (int)a : n;
+    hi = a + per < n ? (int)(a + per) : n;
+}
+
 // Tree sum of the LDS products p[a, e) (thread-strided partial sums, block_sum): the free
 // summation order of a long row's chunk (DevCSR::tree_long).  Result valid in thread 0; every
 // thread of the block must call it.

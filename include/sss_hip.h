@@ -179,8 +179,9 @@ int sss_hip_pcg(sss_hip_hier *h, double tol, int maxit, int *iters, double *relr
 /* AMG-preconditioned flexible GMRES(restart) on level 0, for operators that are not symmetric
  * positive definite (an engine extension, like sss_hip_pcg): right preconditioning with one V-cycle
  * on (v_j, 0) per iteration, Arnoldi by classical Gram-Schmidt applied twice in fused multi-vector
- * kernels (deterministic, no atomics), Givens rotations on the host; one read-back of j + 2 doubles
- * per iteration.  Right-hand side = the level-0 b vector (restored on return), initial guess /
+ * kernels (deterministic, no atomics), Givens rotations on the host; one read-back of j + 3 doubles
+ * per iteration (the Hessenberg column, ||w|| and a stall slot that stays 0 on this engine: the loop
+ * is sss_hip_dist_fgmres's).  Right-hand side = the level-0 b vector (restored on return), initial guess /
  * result = the level-0 x vector.  Stops when the estimate |g_{j+1}| / ||b|| < tol or after maxit
  * iterations in total (restart > maxit is clamped); hist (optional) receives the estimate of each
  * iteration.  ||b|| = 0: x = 0, no iteration.  restart < 1: ERROR_INPUT_PAR; a non-finite norm:
@@ -357,9 +358,10 @@ int sss_hip_dist_download_vec(sss_hip_dist *d, int which, double *own, int n);
 int sss_hip_dist_cycle(sss_hip_dist *d);
 /* global ||b0 - A0 x0||_2 (one 8-byte allreduce), synchronises */
 int sss_hip_dist_residual_norm(sss_hip_dist *d, double *absres);
-/* sss_hip_pcg and sss_hip_fgmres on the row-partitioned engine: the same recurrences (flexible CG
- * with the Polak-Ribiere beta; right-preconditioned FGMRES(restart) with classical Gram-Schmidt
- * applied twice), stop rules, hist / hist_cap / NULL rules and treatment of ||b|| = 0, restart < 1
+/* sss_hip_pcg and sss_hip_fgmres on the row-partitioned engine: for FGMRES the same loop
+ * (right-preconditioned FGMRES(restart) with classical Gram-Schmidt applied twice; one
+ * implementation serves both engines), for PCG the same recurrences (flexible CG with the
+ * Polak-Ribiere beta) in a loop of its own; the same stop rules, hist / hist_cap / NULL rules and treatment of ||b|| = 0, restart < 1
  * (ERROR_INPUT_PAR, before any collective) and a non-finite norm, with "level-0 b / x vector" read
  * as this rank's own rows of them; b is restored on return.  Collective: every rank calls with the
  * same arguments.  z = one sss_hip_dist_cycle on (r, 0) (the captured graph where there is one);
@@ -376,7 +378,8 @@ int sss_hip_dist_residual_norm(sss_hip_dist *d, double *absres);
  * the engine stream) with one small read-back per iteration; over the host transport each reduction
  * synchronises and goes through allreduce_sum; the timing communicator skips them.
  * The iterates are not bitwise the single-GPU solvers': the dot products are summed in another
- * order; every elementwise operation and the whole preconditioner are the same bit for bit.
+ * order; every elementwise operation and the whole preconditioner are the same bit for bit.  (With
+ * one rank FGMRES sums in the single-GPU order and its results are the single-GPU solver's bits.)
  * Workspace is allocated at first use (FGMRES: regrown when restart grows) and freed with the
  * engine: PCG 5 vectors of this rank's rows, FGMRES 2 restart + 3. */
 int sss_hip_dist_pcg(sss_hip_dist *d, double tol, int maxit, int *iters, double *relres, double *hist, int hist_cap);

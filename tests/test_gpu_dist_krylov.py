@@ -274,8 +274,24 @@ def _sc_fgmres_edges(c):
         c.compare(got, ref, b, "fgmres", "maxit 4, restart 3", margin=False)
 
 
+def _sc_same_solver(c):
+    """World 1: the partitioned FGMRES is the single-GPU FGMRES -- one loop, the same kernels on the same
+    rows, a sum over one rank -- so the count, the history and x agree bit for bit, and both restore b."""
+    assert c.world == 1
+    restart = c.cfg["restart"]
+    b, x0 = c.rhs(c.cfg.get("seed", 1)), np.zeros(c.N)
+    its, hist, x = c.solve_dist(b, x0, "fgmres", restart=restart)   # asserts that b came back
+    its1, hist1, x1 = c.solve_single(b, x0, "fgmres", restart=restart)
+    print(f"{c.cfg['name']}: {its} iterations (single GPU {its1})\n  dist   {hist}\n  single {hist1}", flush=True)
+    assert its > 0 and its == its1, (its, its1)
+    assert np.array_equal(_u64(hist), _u64(hist1)), np.flatnonzero(_u64(hist) != _u64(hist1))
+    assert np.array_equal(_u64(x), _u64(x1)), f"max |dx| = {np.max(np.abs(x - x1))}"
+    assert np.array_equal(_u64(c.R.download(0, "b")), _u64(b)), "the single-GPU b was not restored"
+
+
 SCENARIOS = {f.__name__[4:]: f for f in (_sc_solve, _sc_one_sided, _sc_zero_rhs, _sc_exact_guess, _sc_nonfinite_rhs,
-                                          _sc_pcg_edges, _sc_engine_state, _sc_deterministic, _sc_fgmres_edges)}
+                                          _sc_pcg_edges, _sc_engine_state, _sc_deterministic, _sc_fgmres_edges,
+                                          _sc_same_solver)}
 
 
 def _worker(rank, world, port, cfg, errq):
@@ -404,3 +420,17 @@ def test_fgmres_poisson():
 
 def test_fgmres_edges():
     _run(2, kind="convdiff", n=16, smoother="jacobi", agg=100, solver="fgmres", scenario="fgmres_edges")
+
+
+@pytest.mark.parametrize("kind,n,smoother,restart", [
+    ("convdiff", 11, "jacobi", 3),     # 1331 own rows: odd, every basis column padded to even
+    ("convdiff", 11, "jacobi", 20),
+    ("convdiff", 16, "jacobi", 3),     # several restarts
+    ("convdiff", 16, "jacobi", 20),
+    (7, 24, "hybrid", 20),
+])
+@pytest.mark.parametrize("transport", ["host", "rccl"])
+def test_fgmres_world1_is_the_single_gpu_solver(transport, kind, n, smoother, restart):
+    """Both engines run fgmres_solve: at world 1 their results are the same bits."""
+    _run(1, kind=kind, n=n, smoother=smoother, agg=100, solver="fgmres", restart=restart, transport=transport,
+         scenario="same_solver")

@@ -10,6 +10,7 @@
   (graph capture, workspace allocation) and then timed --solve-reps times with a host clock around
   calls that end in a stream synchronise; the median is reported beside every single time (the
   spread of a 50 ms window);
+- the same for DistHierarchy.fgmres at world 1 over RCCL and the single-GPU sss_hip_fgmres (--restart);
 - the reductions' share of a PCG iteration: the same solve with the timing communicator, which
   skips every collective (at world 1 a skipped reduction is the identity, so the iterates are the
   same) -- the difference per iteration is what the three ncclAllReduce calls cost.
@@ -45,6 +46,7 @@ def main() -> int:
     ap.add_argument("--lab-n", type=int, default=1 << 24)
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--maxit", type=int, default=100)
+    ap.add_argument("--restart", type=int, default=20)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--solve-reps", type=int, default=7)
     ap.add_argument("--out", type=Path, default=None)
@@ -85,13 +87,15 @@ def main() -> int:
             E.upload(0, "x", x0)
         E.sync()
 
-    def pcg_timed(E, dist):
+    def pcg_timed(E, dist, solver="pcg"):
+        solve = (lambda: E.pcg(args.tol, args.maxit)) if solver == "pcg" else \
+            (lambda: E.fgmres(args.tol, args.restart, args.maxit))
         start(E, dist)
-        E.pcg(args.tol, args.maxit)   # warm-up
+        solve()   # warm-up
         ts = []
         for _ in range(args.solve_reps):
             start(E, dist)
-            (its, hist), t = timed(lambda: E.pcg(args.tol, args.maxit))
+            (its, hist), t = timed(solve)
             ts.append(t)
         t = float(np.median(ts))
         return {"iterations": its, "seconds": t, "all_seconds": ts, "ms_per_iteration": 1e3 * t / max(its, 1),
@@ -109,6 +113,8 @@ def main() -> int:
     D = A.DistHierarchy(H, comm, device=0, **mode)
     res["dist_pcg_rccl"] = pcg_timed(D, True)
     res["dist_cycle_graph"] = D.level_flags(0)["cycle_graph"]
+    res["dist_fgmres_rccl"] = pcg_timed(D, True, "fgmres")
+    print(f"[dist fgmres] {res['dist_fgmres_rccl']}", file=sys.stderr, flush=True)
     print(f"[dist pcg] {res['dist_pcg_rccl']}", file=sys.stderr, flush=True)
 
     def vloop():
@@ -146,8 +152,9 @@ def main() -> int:
 
     S = A.DeviceHierarchy(H, device=0, **mode)
     res["single_gpu_pcg"] = pcg_timed(S, False)
+    res["single_gpu_fgmres"] = pcg_timed(S, False, "fgmres")
     S.close()
-    print(f"[single-GPU pcg] {res['single_gpu_pcg']}", file=sys.stderr, flush=True)
+    print(f"[single-GPU pcg] {res['single_gpu_pcg']}\n[single-GPU fgmres] {res['single_gpu_fgmres']}", file=sys.stderr, flush=True)
     dist.destroy_process_group()
 
     text = json.dumps(res, indent=1)
