@@ -840,8 +840,7 @@ static int dist_cycle_enqueue(sss_hip_dist *d)
         double *xc = l + 1 < nagg ? d->L[l + 1].x : hier_vec(d->tail, 0, SSS_HIP_VEC_X);
         // dead F-row correction (see walk_cycle in sss_hier.hip): prolong into the C rows only
         const bool tile = !L.P.wave_rows && !L.P.vec_rows;
-        const bool dead_f = L.sm.f_overwritten && d->pars.post_iter > 0 && L.P.split_row == L.sm.pass[0].hi &&
-                            L.P.split_row > 0 && tile;
+        const bool dead_f = prolong_c_rows_only(L.sm, L.P, d->pars.post_iter) && tile;
         int lrc = 0;
         auto prolong = [&](int b0, int b1) {
             lrc = lrc ? lrc : launch_spmv_range(L.P, b0, b1, SSS_HIP_SPMV_AMXPY, 1.0, xc, nullptr, L.x, nullptr, s);

@@ -597,6 +597,12 @@ struct SmootherPlan {
     // Every value of A is finite: a pass over a zero iterate reduces to t = b (zero_first_pass).
     bool finite = false;
 };
+// The post-smoother's first pass overwrites every F row from C values only, so the F rows' coarse
+// correction is dead: the prolongation P of the level may be applied to its C rows alone.
+inline bool prolong_c_rows_only(const SmootherPlan &sp, const DevCSR &P, int post_iter)
+{
+    return sp.f_overwritten && post_iter > 0 && P.split_row == sp.pass[0].hi && P.split_row > 0;
+}
 // Residual fused into the smoother's last pass: r[i] = b[i] - sum_k a_ik x_k (stored order from
 // 0.0, x after the pass) for the C rows, and their per-block sums of squares into partial[block]
 // when partial is given; the caller then forms the F rows' residual (blocks [0, split_blk)).

@@ -1047,12 +1047,11 @@ static int walk_cycle(sss_hip_hier *h, CoarseFn coarse, bool pend = false)
             // x_l += P e.  When the post-smoother's first pass overwrites every F row from C values
             // only (depth-1 GS F pass, all |d| > 1e-20), the F rows' correction is dead: prolong
             // into the C rows only (the iterates are bitwise unchanged).
-            if (L.sm.f_overwritten && h->pars.post_iter > 0 && L.P.split_row == L.sm.pass[0].hi &&
-                L.P.split_row > 0 && L.pinj) {
+            const bool c_only = prolong_c_rows_only(L.sm, L.P, h->pars.post_iter);
+            if (c_only && L.pinj) {
                 if ((rc = launch_prolong_inject(L.P.n - L.P.split_row, L.P.split_row, L.pinj, h->L[l + 1].x, L.x, s)))
                     return rc;
-            } else if (L.sm.f_overwritten && h->pars.post_iter > 0 && L.P.split_row == L.sm.pass[0].hi &&
-                L.P.split_row > 0 && !L.P.wave_rows && !L.P.vec_rows) {
+            } else if (c_only && !L.P.wave_rows && !L.P.vec_rows) {
                 if ((rc = launch_spmv_range(L.P, L.P.split_blk, L.P.nblk, SSS_HIP_SPMV_AMXPY, 1.0, h->L[l + 1].x, nullptr,
                                             L.x, nullptr, s)))
                     return rc;

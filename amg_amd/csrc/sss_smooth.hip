@@ -18,348 +18,186 @@
 //
 // C/F-Jacobi (engine extension; SSS_SM_JACOBI): F pass then C pass, every row of a pass
 // reading the values from before the pass (ping-pong buffers), d = the row's last diagonal.
-#include "sss_engine.hpp"
+#include "sss_smooth_plan.hpp"
 #include "sss_spmv_dev.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <type_traits>
 #include <cmath>
 
 namespace sss {
 
-// ---- host-side planning ---------------------------------------------------------------------
+// ---- plan upload: each step builds on the host (sss_smooth_plan.hip), uploads, sets the plan's
+// fields and lets its host arrays go ------------------------------------------------------------
 static const char *const kPlanArray = "hipMalloc(plan array)";   // the error line of a failed plan upload
+
+static int alloc_vec(double *&p, size_t count, const char *what, int line = __builtin_LINE())
+{
+    p = dev_alloc<double>(count);
+    return p ? 0 : hip_fail(hipErrorOutOfMemory, what, __FILE__, line);
+}
+
+// exact GS depth launches hold few rows each: a wave per row pays from short lengths on
+static bool long_rows_of(long long nnz, int rows) { return rows > 0 && nnz >= (long long)std::min(32, wave_row_min()) * rows; }
+
+static int upload_buckets(PassSchedule &ps, DepthBuckets &bk)
+{
+    ps.depth = bk.depth, ps.nrows = bk.nrows, ps.max_width = bk.max_width;
+    ps.h_off = std::move(bk.h_off);
+    return dev_upload(ps.rows, bk.rows, kPlanArray);
+}
+
+// contiguous class?  (relabeled level: F rows first, then C rows): the pass runs on the level matrix's
+// own row blocks; C/F-Jacobi gets the iterate buffers of the class
+static int setup_range(PassSchedule &ps, const ClassRange &r, int kind, int inner)
+{
+    if (!r.contiguous) return 0;
+    ps.range = r.blocks, ps.blo = r.blo, ps.bhi = r.bhi, ps.lo = r.lo, ps.hi = r.hi;
+    if (!ps.range || kind != SSS_HIP_SMOOTH_JACOBI) return 0;
+    int rc = alloc_vec(ps.y, (size_t)(r.hi - r.lo), "hipMalloc(y)");
+    if (!rc && inner > 0) rc = alloc_vec(ps.y2, (size_t)(r.hi - r.lo), "hipMalloc(y2)");
+    return rc;
+}
+
+static int upload_compact(PassSchedule &ps, const SSS_MAT &A, const int *cls, int c, int kind)
+{
+    CompactRows cr;
+    build_compact_rows(A, cls, c, cr);
+    const SSS_MAT sub = cr.mat(A.num_cols);
+    int rc;
+    if ((rc = devcsr_upload(ps.sub, sub)) || (rc = dev_upload(ps.map, cr.map, kPlanArray))) return rc;
+    return kind == SSS_HIP_SMOOTH_JACOBI ? alloc_vec(ps.y, cr.map.size(), "hipMalloc(y)") : 0;
+}
+
+// exact GS passes with intra-class chains: one launch per pass where the class is contiguous; then
+// every pass of a call in one launch (both passes on the flow engine; 2 sweeps, SSS_amg_pars_init's
+// pre/post count)
+static int build_one_launch(SmootherPlan &sp, const SSS_MAT &A, const int *mark, const DevCSR *dA, const int *cls,
+                            const SmootherSwitches &sw)
+{
+    int rc;
+    for (int c = 0; c < 2; ++c) {
+        PassSchedule &ps = sp.pass[c];
+        if (ps.compact || ps.depth <= 1 || ps.nrows == 0) continue;
+        const ClassRange r = class_range(cls, A.num_rows, c);
+        if (r.contiguous && (rc = gs_persist_build(ps, A, r.lo, r.hi, sp.long_rows))) return rc;
+    }
+    if (sw.gs_fused && mark && sp.pass[0].gp.engine == 1 && sp.pass[1].gp.engine == 1)
+        return gs_fused_build(sp.fz, A, dA, sp.pass, cls, 2);
+    return 0;
+}
+
+static int upload_two_stage(PassSchedule &ps, const SSS_MAT &A, int c, const int *gcls, int enc, PhaseTimer &pt)
+{
+    const int m = ps.hi - ps.lo;
+    TwoStageSplit ts;
+    two_stage_count(A, ps.lo, m, c, gcls, ts);
+    pt.mark("ts count");
+    two_stage_fill(A, ps.lo, m, c, gcls, ts);
+    pt.mark("ts fill");
+    const SSS_MAT Mn = ts.Mn(A.num_cols), Ml = ts.Ml(A.num_cols);
+    // read by the ts_* kernels only: merged groups, or the column ELL
+    const int tenc = (enc & ~kEncDict) | kEncMergedOnly;
+    int rc;
+    if ((rc = devcsr_upload(ps.ts_nl, Mn, -1, tenc, ts.split.data())) || (rc = devcsr_upload(ps.ts_lo, Ml, -1, tenc)))
+        return rc;
+    pt.mark("ts upload");
+    if ((rc = dev_upload(ps.ts_split, ts.split, kPlanArray))) return rc;
+    return alloc_vec(ps.ts_P, (size_t)m, "hipMalloc(P)");
+}
 
 int smoother_build(SmootherPlan &sp, const SSS_MAT &A, const int *mark, int kind, const DevCSR *dA, int inner,
                    const int *gcls, int enc)
 {
     const int n = A.num_rows;
-    const int *rp = A.row_ptr, *ci = A.col_idx;
-    const double *v = A.val;
-    // per-row arrays filled by the row-parallel pass below (no serial zero-fill of n-length arrays)
-    HostBuf<int> cls, depth, pushed, diag_pos;
-    HostBuf<double> last_diag, d_first_buf, d_later_buf;
-    HostBuf<char> has_diag;
-    cls.resize(n), depth.resize(n), pushed.resize(n), diag_pos.resize(n), last_diag.resize(n), has_diag.resize(n);
-    bool all_diag = true, single_diag = true;
-    int rc;
-    const char *tz = getenv("SSS_HIP_TILE_DIAG");   // 0: divisors from the deff stream (tests)
-
-    const bool timing = getenv("SSS_HIP_TIMING") != nullptr;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now(), t_sched = 0, t_persist = 0, t_two = 0;
-    sp.kind = kind;
-    {   // classes, diagonals (row-parallel)
-        std::atomic<bool> all{true}, single{true};
-        parallel_chunks(n, 1 << 16, [&](int lo, int hi) {
-            bool a = true, s1 = true;
-            for (int i = lo; i < hi; ++i) {
-                cls[i] = mark ? (mark[i] == 1 ? 1 : 0) : 0;
-                depth[i] = pushed[i] = 0;
-                last_diag[i] = 0.0;
-                has_diag[i] = 0;
-                diag_pos[i] = -1;
-                for (int k = rp[i]; k < rp[i + 1]; ++k)
-                    if (ci[k] == i) {
-                        last_diag[i] = v[k];
-                        if (has_diag[i]) s1 = false;
-                        has_diag[i] = 1;
-                        diag_pos[i] = k;
-                    }
-                a = a && has_diag[i];
-            }
-            if (!a) all = false;
-            if (!s1) single = false;
-        });
-        all_diag = all;
-        single_diag = single;
-    }
-    // stale-d resolution: simulate the divisor register over two sweeps of (F pass, C pass); with
-    // a diagonal in every row it is each row's own last diagonal entry
-    const double *d_first = last_diag.data(), *d_later = last_diag.data();
-    if (!all_diag) {
-        d_first_buf.resize(n), d_later_buf.resize(n);
-        d_first = d_first_buf.data(), d_later = d_later_buf.data();
-        double d = 0.0;
-        for (int sweep = 0; sweep < 2; ++sweep)
-            for (int c = 0; c < 2; ++c)
-                for (int i = 0; i < n; ++i) {
-                    if (cls[i] != c) continue;
-                    if (has_diag[i]) d = last_diag[i];
-                    (sweep == 0 ? d_first_buf : d_later_buf)[i] = d;
-                }
-    }
-    // level schedule per class
-    long long nnz_total = rp[n];
-    // exact GS depth launches hold few rows each: a wave per row pays from short lengths on
-    sp.long_rows = n > 0 && nnz_total >= (long long)std::min(32, wave_row_min()) * n;
-    std::atomic<bool> coupled{false};   // any same-class off-diagonal entry at all?
-    parallel_chunks(n, 1 << 16, [&](int lo, int hi) {
-        for (int i = lo; i < hi && !coupled; ++i)
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = ci[k];
-                if (j != i && j < n && cls[j] == cls[i]) {
-                    coupled = true;
-                    break;
-                }
-            }
-    });
+    const bool jacobi = kind == SSS_HIP_SMOOTH_JACOBI;
+    const SmootherSwitches sw = smoother_switches();
     PhaseTimer pt("plan");
+    double lap[5] = {PhaseTimer::now()};
+    int rc;
+    sp.kind = kind;
+    RowClasses rw;
+    plan_row_classes(A, mark, rw);
+    StaleDivisors stale;
+    plan_stale_divisors(rw, n, stale);
+    sp.long_rows = long_rows_of(A.row_ptr[n], n);
+    const bool coupled = plan_coupled(A, rw);
     pt.mark("classes+coupled");
     // red-black levels (no coupling) keep depth 0 everywhere; so do C/F-Jacobi levels, whose
     // passes read only the other iterate (their schedule is never walked by depth)
-    if (coupled && kind != SSS_HIP_SMOOTH_JACOBI) {
-        for (int i = 0; i < n; ++i) {
-            int dep = pushed[i];
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = ci[k];
-                if (j < i && cls[j] == cls[i]) dep = std::max(dep, depth[j] + 1);
-            }
-            depth[i] = dep;
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = ci[k];
-                if (j > i && j < n && cls[j] == cls[i]) pushed[j] = std::max(pushed[j], dep + 1);
-            }
-        }
-    }
+    if (coupled && !jacobi) schedule_classes(A, rw);
     pt.mark("depth");
     for (int c = 0; c < 2; ++c) {
         PassSchedule &ps = sp.pass[c];
-        int maxd = -1;
-        for (int i = 0; i < n; ++i)
-            if (cls[i] == c) maxd = std::max(maxd, depth[i]);
-        ps.depth = maxd + 1;
-        ps.h_off.assign(ps.depth + 1, 0);
-        for (int i = 0; i < n; ++i)
-            if (cls[i] == c) ps.h_off[depth[i] + 1]++;
-        for (int l = 0; l < ps.depth; ++l) {
-            ps.max_width = std::max(ps.max_width, ps.h_off[l + 1]);
-            ps.h_off[l + 1] += ps.h_off[l];
-        }
-        ps.nrows = ps.depth > 0 ? ps.h_off[ps.depth] : 0;
-        std::vector<int> fill(ps.h_off.begin(), ps.h_off.end()), rows(std::max(ps.nrows, 1));
-        for (int i = 0; i < n; ++i)
-            if (cls[i] == c) rows[fill[depth[i]]++] = i;
-        if ((rc = dev_upload(ps.rows, rows, kPlanArray))) return rc;
-        ps.compact = kind == SSS_HIP_SMOOTH_JACOBI || ps.depth <= 1;
-        if (ps.compact && ps.nrows > 0 && dA && single_diag) {
-            // contiguous class?  (relabeled level: F rows first, then C rows)
-            int lo = -1, hi = -1;
-            bool contiguous = true;
-            for (int i = 0; i < n && contiguous; ++i) {
-                if (cls[i] != c) continue;
-                if (lo < 0) lo = i;
-                else if (i != hi) contiguous = false;
-                hi = i + 1;
-            }
-            if (contiguous) {
-                // the pass must be a whole number of the level's row blocks
-                if (lo == 0 && hi == n) ps.range = true, ps.blo = 0, ps.bhi = dA->nblk;
-                else if (lo == 0 && hi == dA->split_row) ps.range = true, ps.blo = 0, ps.bhi = dA->split_blk;
-                else if (lo == dA->split_row && hi == n) ps.range = true, ps.blo = dA->split_blk, ps.bhi = dA->nblk;
-                ps.lo = lo;
-                ps.hi = hi;
-            }
-            if (ps.range && kind == SSS_HIP_SMOOTH_JACOBI) {
-                ps.y = dev_alloc<double>((size_t)(hi - lo));
-                if (!ps.y) return hip_fail(hipErrorOutOfMemory, "hipMalloc(y)", __FILE__, __LINE__);
-                if (inner > 0) {
-                    ps.y2 = dev_alloc<double>((size_t)(hi - lo));
-                    if (!ps.y2) return hip_fail(hipErrorOutOfMemory, "hipMalloc(y2)", __FILE__, __LINE__);
-                }
-            }
-        }
-        if (ps.compact && ps.nrows > 0 && !ps.range) {
-            std::vector<int> crp(1, 0), cci, cmap;
-            std::vector<double> cv;
-            for (int i = 0; i < n; ++i) {
-                if (cls[i] != c) continue;
-                cmap.push_back(i);
-                for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                    cci.push_back(ci[k] == i ? -1 : ci[k]);   // diagonal -> product +0.0 (identity)
-                    cv.push_back(v[k]);
-                }
-                crp.push_back((int)cci.size());
-            }
-            SSS_MAT sub;
-            sub.num_rows = (int)cmap.size();
-            sub.num_cols = A.num_cols;
-            sub.num_nnzs = (int)cci.size();
-            sub.row_ptr = crp.data();
-            sub.col_idx = cci.data();
-            sub.val = cv.data();
-            if ((rc = devcsr_upload(ps.sub, sub))) return rc;
-            if ((rc = dev_upload(ps.map, cmap, kPlanArray))) return rc;
-            if (kind == SSS_HIP_SMOOTH_JACOBI) {
-                ps.y = dev_alloc<double>(cmap.size());
-                if (!ps.y) return hip_fail(hipErrorOutOfMemory, "hipMalloc(y)", __FILE__, __LINE__);
-            }
-        }
-    }
-    if ((rc = dev_upload(sp.cls, cls, kPlanArray))) return rc;
-    t_sched = now();
-    // exact GS passes with intra-class chains: one launch per pass where the class is contiguous
-    if (kind == SSS_HIP_SMOOTH_EXACT && !gcls && A.num_cols == n) {
-        for (int c = 0; c < 2; ++c) {
-            PassSchedule &ps = sp.pass[c];
-            if (ps.compact || ps.depth <= 1 || ps.nrows == 0) continue;
-            int lo = -1, hi = -1;
-            bool contiguous = true;
-            for (int i = 0; i < n && contiguous; ++i) {
-                if (cls[i] != c) continue;
-                if (lo < 0) lo = i;
-                else if (i != hi) contiguous = false;
-                hi = i + 1;
-            }
-            if (contiguous && (rc = gs_persist_build(ps, A, lo, hi, sp.long_rows))) return rc;
-        }
-    }
-    {   // every pass of a call in one launch (exact GS-CF, both passes on the flow engine; 2 sweeps,
-        // SSS_amg_pars_init's pre/post count)
-        const char *fe = getenv("SSS_HIP_GS_FUSED");   // 0: per-pass launches (tests compare both)
-        if (!(fe && *fe == '0') && kind == SSS_HIP_SMOOTH_EXACT && !gcls && A.num_cols == n && mark &&
-            sp.pass[0].gp.engine == 1 && sp.pass[1].gp.engine == 1 &&
-            (rc = gs_fused_build(sp.fz, A, dA, sp.pass, cls.data(), 2)))
+        DepthBuckets bk;
+        bucket_rows(0, n, rw.cls.data(), c, rw.depth.data(), bk);
+        if ((rc = upload_buckets(ps, bk))) return rc;
+        ps.compact = jacobi || ps.depth <= 1;
+        if (ps.compact && ps.nrows > 0 && dA && rw.single_diag &&
+            (rc = setup_range(ps, class_range(rw.cls.data(), n, c, dA), kind, inner)))
             return rc;
+        if (ps.compact && ps.nrows > 0 && !ps.range && (rc = upload_compact(ps, A, rw.cls.data(), c, kind))) return rc;
     }
-    t_persist = now();
-    if (kind == SSS_HIP_SMOOTH_JACOBI && inner > 0 && sp.pass[0].range == (sp.pass[0].nrows > 0) &&
-        sp.pass[1].range == (sp.pass[1].nrows > 0)) {
+    if ((rc = dev_upload(sp.cls, rw.cls, kPlanArray))) return rc;
+    lap[1] = PhaseTimer::now();
+    if (kind == SSS_HIP_SMOOTH_EXACT && !gcls && A.num_cols == n && (rc = build_one_launch(sp, A, mark, dA, rw.cls.data(), sw)))
+        return rc;
+    lap[2] = PhaseTimer::now();
+    if (jacobi && inner > 0 && sp.pass[0].range == (sp.pass[0].nrows > 0) && sp.pass[1].range == (sp.pass[1].nrows > 0)) {
         sp.inner = inner;
-        for (auto &ps : sp.pass) {
-            if (ps.nrows == 0) continue;
-            const int m = ps.hi - ps.lo;
-            const int c = (int)(&ps - sp.pass);
-            // L_i: same class, j < i in the global order -- own rows of the pass below i, or
-            // (distributed levels) ghost columns of this class owned by lower ranks
-            auto lower = [&](int i, int j) { return j < n ? (j >= ps.lo && j < i) : (gcls && gcls[j - n] == c); };
-            // two row-parallel passes: count, then fill at the prefix offsets (same order as a
-            // sequential build: N_i entries in stored order, then L_i entries in stored order)
-            std::vector<int> nrp((size_t)m + 1, 0), lrp((size_t)m + 1, 0), split(m);
-            parallel_chunks(m, 1 << 12, [&](int a, int e) {
-                for (int q = a; q < e; ++q) {
-                    const int i = ps.lo + q;
-                    int nn = 0, nl = 0;
-                    for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                        const int j = ci[k];
-                        if (lower(i, j)) ++nl;
-                        else if (j != i) ++nn;
-                    }
-                    nrp[q + 1] = nn + nl;
-                    lrp[q + 1] = nl;
-                }
-            });
-            for (int q = 0; q < m; ++q) nrp[q + 1] += nrp[q], lrp[q + 1] += lrp[q];
-            pt.mark("ts count");
-            HostBuf<int> nci, lci;   // every slot written below (no serial zero-fill)
-            HostBuf<double> nv, lv;
-            nci.resize((size_t)nrp[m]), lci.resize((size_t)lrp[m]), nv.resize((size_t)nrp[m]), lv.resize((size_t)lrp[m]);
-            parallel_chunks(m, 1 << 12, [&](int a, int e) {
-                for (int q = a; q < e; ++q) {
-                    const int i = ps.lo + q;
-                    int o = nrp[q], ol = lrp[q];
-                    for (int k = rp[i]; k < rp[i + 1]; ++k) {   // N_i: off-diagonal, not same-class lower
-                        const int j = ci[k];
-                        if (j != i && !lower(i, j)) nci[o] = j, nv[o] = v[k], ++o;
-                    }
-                    split[q] = o;
-                    for (int k = rp[i]; k < rp[i + 1]; ++k) {   // L_i
-                        const int j = ci[k];
-                        if (lower(i, j)) {
-                            nci[o] = j, nv[o] = v[k], ++o;
-                            lci[ol] = j, lv[ol] = v[k], ++ol;
-                        }
-                    }
-                }
-            });
-            auto mk = [&](std::vector<int> &r, HostBuf<int> &c, HostBuf<double> &w) {
-                SSS_MAT M;
-                M.num_rows = m;
-                M.num_cols = A.num_cols;
-                M.num_nnzs = (int)c.size();
-                M.row_ptr = r.data();
-                M.col_idx = c.data();
-                M.val = w.data();
-                return M;
-            };
-            pt.mark("ts fill");
-            SSS_MAT Mn = mk(nrp, nci, nv), Ml = mk(lrp, lci, lv);
-            std::vector<int> seg(split);   // absolute [N_i | L_i] cut of each row of Mn
-            // read by the ts_* kernels only: merged groups, or the column ELL
-            const int tenc = (enc & ~kEncDict) | kEncMergedOnly;
-            if ((rc = devcsr_upload(ps.ts_nl, Mn, -1, tenc, seg.data())) || (rc = devcsr_upload(ps.ts_lo, Ml, -1, tenc)))
-                return rc;
-            pt.mark("ts upload");
-            if ((rc = dev_upload(ps.ts_split, split, kPlanArray))) return rc;
-            ps.ts_P = dev_alloc<double>((size_t)m);
-            if (!ps.ts_P) return hip_fail(hipErrorOutOfMemory, "hipMalloc(P)", __FILE__, __LINE__);
-        }
+        for (int c = 0; c < 2; ++c)
+            if (sp.pass[c].nrows > 0 && (rc = upload_two_stage(sp.pass[c], A, c, gcls, enc, pt))) return rc;
     }
-    t_two = now();
+    lap[3] = PhaseTimer::now();
     if (sp.pass[0].range || sp.pass[1].range)
-        if ((rc = dev_upload(sp.diag_pos, diag_pos, kPlanArray))) return rc;
-    const char *nc = getenv("SSS_HIP_NOCOPY");   // 0: C/F-Jacobi through per-pass copies (tests)
-    if (!(nc && *nc == '0') && kind == SSS_HIP_SMOOTH_JACOBI && !gcls && A.num_cols == n) {
-        const PassSchedule &F = sp.pass[0], &Cp = sp.pass[1];
-        const bool f_ok = F.nrows == 0 || (F.range && F.lo == 0), c_ok = Cp.nrows == 0 || (Cp.range && Cp.hi == n);
-        const int cs = F.nrows > 0 ? F.hi : 0;
-        if (f_ok && c_ok && (Cp.nrows == 0 || Cp.lo == cs) && (F.nrows > 0 || Cp.nrows > 0)) {
-            sp.csplit = cs;
-            sp.x2 = dev_alloc<double>((size_t)n);
-            if (!sp.x2) return hip_fail(hipErrorOutOfMemory, "hipMalloc(x2)", __FILE__, __LINE__);
-        }
+        if ((rc = dev_upload(sp.diag_pos, rw.diag_pos, kPlanArray))) return rc;
+    if (const int cs = plan_nocopy_split(sp, A, gcls, sw); cs >= 0) {
+        sp.csplit = cs;
+        if ((rc = alloc_vec(sp.x2, (size_t)n, "hipMalloc(x2)"))) return rc;
     }
-    sp.own_diag = all_diag && single_diag && !(tz && *tz == '0');
-    {
-        const char *zz = getenv("SSS_HIP_ZERO_FIRST");   // 0: run the first pass on a zero x in full (tests)
-        std::atomic<bool> fin{!(zz && *zz == '0')};
-        if (fin)
-            parallel_chunks(n, 1 << 16, [&](int lo, int hi) {
-                for (int k = rp[lo]; k < rp[hi] && fin; ++k)
-                    if (!std::isfinite(v[k])) fin = false;
-            });
-        sp.finite = fin;
-    }
-    {
-        const char *dz = getenv("SSS_HIP_DEAD_PROLONG");   // 0: always prolong into every row (tests)
-        const PassSchedule &F = sp.pass[0];
-        bool ok = !(dz && *dz == '0') && kind != SSS_HIP_SMOOTH_JACOBI && F.range && F.lo == 0 && F.nrows > 0 &&
-                  F.depth <= 1 && single_diag;
-        for (int i = F.lo; ok && i < F.hi; ++i)
-            ok = std::fabs(d_first[i]) > SMALLFLOAT && std::fabs(all_diag ? d_first[i] : d_later[i]) > SMALLFLOAT;
-        sp.f_overwritten = ok;
-    }
-    const char *fz = getenv("SSS_HIP_FUSE_RESID");
-    const char *pz = getenv("SSS_HIP_PEND_F");   // 0: never precompute the first F pass (tests)   // 0: never fuse (tests compare both paths)
-    if (!(fz && *fz == '0') && kind != SSS_HIP_SMOOTH_JACOBI && dA && !dA->wave_rows && !dA->vec_rows && all_diag && single_diag &&
-        dA->split_row > 0 &&
-        dA->split_row < n && sp.pass[0].range && sp.pass[1].range && sp.pass[0].lo == 0 &&
-        sp.pass[0].hi == dA->split_row && sp.pass[1].lo == dA->split_row && sp.pass[1].hi == n) {
-        // the MODE 2 / 3 passes have no long-row path: every block of the pass within one tile (the
-        // ELL formats take one row per thread and rows of at most 32 entries)
-        std::vector<int> blk;
-        const bool ell = dA->dv_ell || dA->dv_xell;
-        if (!ell) build_row_blocks(rp, n, blk, dA->split_row);
-        bool short_blocks = true;
-        for (int q = dA->split_blk; !ell && q < dA->nblk && short_blocks; ++q)
-            short_blocks = rp[blk[q + 1]] - rp[blk[q]] <= kTileEntries;
-        sp.fuse_resid = short_blocks;
-        bool f_short = true;
-        for (int q = 0; !ell && q < dA->split_blk && f_short; ++q) f_short = rp[blk[q + 1]] - rp[blk[q]] <= kTileEntries;
-        sp.pend_ok = short_blocks && f_short && sp.f_overwritten && !(pz && *pz == '0');
-    }
-    if (timing)
+    const double *d_first = rw.all_diag ? rw.last_diag.data() : stale.first.data();
+    const double *d_later = rw.all_diag ? rw.last_diag.data() : stale.later.data();
+    sp.own_diag = plan_own_diag(rw, sw);
+    sp.finite = plan_finite(A, sw);
+    sp.f_overwritten = plan_f_overwritten(sp, rw, d_first, d_later, sw);
+    plan_fused_flags(sp, A, dA, rw, sw);
+    lap[4] = PhaseTimer::now();
+    if (getenv("SSS_HIP_TIMING"))
         fprintf(stderr, "[sss_hip]   smoother plan n=%d: schedule %.2f s, one-launch GS %.2f s, two-stage %.2f s, rest %.2f s\n",
-                n, t_sched - t0, t_persist - t_sched, t_two - t_persist, now() - t_two);
-    if (kind == SSS_HIP_SMOOTH_JACOBI || all_diag) {   // Jacobi: row's own diagonal
-        if ((rc = dev_upload(sp.d_first, last_diag, kPlanArray))) return rc;
+                n, lap[1] - lap[0], lap[2] - lap[1], lap[3] - lap[2], lap[4] - lap[3]);
+    if (jacobi || rw.all_diag) {   // Jacobi: row's own diagonal
+        if ((rc = dev_upload(sp.d_first, rw.last_diag, kPlanArray))) return rc;
         sp.d_later = sp.d_first;
     } else {
-        if ((rc = dev_upload(sp.d_first, d_first_buf, kPlanArray))) return rc;
-        if ((rc = dev_upload(sp.d_later, d_later_buf, kPlanArray))) return rc;
+        if ((rc = dev_upload(sp.d_first, stale.first, kPlanArray))) return rc;
+        if ((rc = dev_upload(sp.d_later, stale.later, kPlanArray))) return rc;
     }
+    return 0;
+}
+
+int smoother_build_natural(SmootherPlan &sp, const SSS_MAT &A, int lo, int hi)
+{
+    int rc;
+    sp.kind = SSS_HIP_SMOOTH_EXACT;
+    sp.natural = true;
+    sp.long_rows = long_rows_of(A.row_ptr[hi] - A.row_ptr[lo], hi - lo);
+    NaturalDivisors nd;
+    plan_natural_divisors(A, lo, hi, nd);
+    // level schedules: ascending (row i reads the new x_j of coupled j < i, the old x_j of j > i,
+    // which must wait for it) and descending (mirrored)
+    for (int dir = 0; dir < 2; ++dir) {
+        PassSchedule &ps = sp.pass[dir];
+        std::vector<int> depth;
+        schedule_natural(A, lo, hi, dir == 1, depth);
+        DepthBuckets bk;
+        bucket_rows(lo, hi, nullptr, 0, depth.data(), bk);
+        if ((rc = upload_buckets(ps, bk))) return rc;
+        if (ps.depth > 1 && (rc = gs_persist_build(ps, A, lo, hi, sp.long_rows, true, dir == 1))) return rc;
+    }
+    if ((rc = dev_upload(sp.d_first, nd.first[0], kPlanArray)) || (rc = dev_upload(sp.d_later, nd.later[0], kPlanArray)) ||
+        (rc = dev_upload(sp.nd_first, nd.first[1], kPlanArray)) || (rc = dev_upload(sp.nd_later, nd.later[1], kPlanArray)))
+        return rc;
     return 0;
 }
 
@@ -1196,18 +1034,29 @@ __global__ __launch_bounds__(kBlock) void zero_first_pass(int lo, int m, const i
     y[q] = div_ok(d) ? t / d : 0.0;   // a row that keeps its value keeps x_r = +0.0
 }
 
+// The tile-path relaxation (relax_range, MODE M) of the row blocks [b0, b1) of pass ps: new values into
+// y (MODE 0 / 2: into x), the divisor from the staged diagonal when deff is null; MODE 2 / 3 also write
+// the rows' residual r and its per-block sums of squares.
+template <int M>
+static void launch_tile(const SmootherPlan &sp, const DevCSR &A, const PassSchedule &ps, int b0, int b1, const double *b,
+                        double *x, double *y, const double *deff, double *r, double *partial, XSrc xs, hipStream_t s)
+{
+    with_tile_kind(A, [&](auto K) {
+        launch_relax_range<M, decltype(K)::value>(b0, b1 - b0, s, devdict(A, 0), A.bk, A.rp, A.ci, A.v, sp.diag_pos, ps.lo,
+                                                  b, x, (const double *)nullptr, y, deff, A.pk, A.pv, A.pb, r, partial, xs);
+    });
+}
+// tile passes take each row's divisor from its staged diagonal (no deff stream)
+static bool tile_diag(const SmootherPlan &sp, const DevCSR &A) { return sp.own_diag && (A.pk != nullptr || has_dict(A)); }
+
 int launch_f_residual_pending(const SmootherPlan &sp, const DevCSR &A, const double *b, const double *x, double *r,
                               double *partial, double *pend, hipStream_t s)
 {
     if (!sp.pend_ok) return ERROR_INPUT_PAR;
     const PassSchedule &F = sp.pass[0];
-    const double *deff = (sp.own_diag && (A.pk || has_dict(A))) ? nullptr : sp.d_first;
+    const double *deff = tile_diag(sp, A) ? nullptr : sp.d_first;
     ledger_pass(A, F, deff ? 40.0 : 32.0);   // b, r, pend (and deff)
-    with_tile_kind(A, [&](auto K) {
-        launch_relax_range<3, decltype(K)::value>(F.blo, F.bhi - F.blo, s, devdict(A, 0), A.bk, A.rp, A.ci, A.v,
-                                                  sp.diag_pos, F.lo, b, const_cast<double *>(x), (const double *)nullptr,
-                                                  pend, deff, A.pk, A.pv, A.pb, r, partial, xsrc_of(x));
-    });
+    launch_tile<3>(sp, A, F, F.blo, F.bhi, b, const_cast<double *>(x), pend, deff, r, partial, xsrc_of(x), s);
     SSS_HIP(hipGetLastError());
     return 0;
 }
@@ -1238,268 +1087,279 @@ static int depth_launches(const PassSchedule &ps, bool long_rows, bool nat, cons
     return 0;
 }
 
-int smoother_build_natural(SmootherPlan &sp, const SSS_MAT &A, int lo, int hi)
+// ---- smoother_run: decide the form of each pass, then run it --------------------------------------
+enum class PassForm {
+    Skip,            // no rows, or the first F pass came with the last residual (pre_f)
+    TwoStageHooks,   // two-stage on a distributed level: iterates in the hooks' full-length vectors
+    NoCopy,          // C/F-Jacobi or two-stage alternating between x and the plan's x2
+    TwoStage,        // two-stage through y / y2, copied back
+    ZeroFirst,       // C/F-Jacobi on a zero x, in place
+    Jacobi,          // C/F-Jacobi through y, copied back
+    FusedResid,      // exact range pass that also writes its rows' residual (MODE 2)
+    Range,           // exact range pass (MODE 0)
+    CompactJacobi,   // C/F-Jacobi on the class's sub-CSR + scatter
+    CompactExact,    // exact depth-1 pass on the class's sub-CSR
+    Flow,            // one-launch exact pass
+    Depths           // one launch per DAG depth
+};
+// What of a smoother_run call decides the form of its passes.
+struct PassCall {
+    bool hooks, halo_split;   // PassHooks given; with a split hook
+    bool x_zero, resid, pre_f, wave, nocopy;
+    int sweeps;
+};
+struct PassChoice {
+    PassForm form;
+    bool zfirst;   // first pass on a just-zeroed iterate (C/F-Jacobi / two-stage): t = b, no matrix read
+    bool split;    // a plain tile-path relaxation pass (exact depth-1 GS-CF, or C/F-Jacobi) overlaps the
+                   // halo with its interior blocks (PassHooks::split)
+};
+static PassChoice pass_form(const SmootherPlan &sp, int c, int sw, const PassCall &k)
 {
-    const int n = A.num_rows, m = hi - lo;
-    const int *rp = A.row_ptr, *ci = A.col_idx;
-    const double *v = A.val;
-    int rc;
-    sp.kind = SSS_HIP_SMOOTH_EXACT;
-    sp.natural = true;
-    long long nnz = 0;
-    for (int i = lo; i < hi; ++i) nnz += rp[i + 1] - rp[i];
-    sp.long_rows = m > 0 && nnz >= (long long)std::min(32, wave_row_min()) * m;
-    // the carried reciprocal d (Solve/SSS_smooth.c:106-109): per direction, first sweep from
-    // d = 0, later sweeps from the previous sweep's last value
-    std::vector<double> df[2] = {std::vector<double>(n, 0.0), std::vector<double>(n, 0.0)},
-                        dl[2] = {std::vector<double>(n, 0.0), std::vector<double>(n, 0.0)};
-    for (int dir = 0; dir < 2; ++dir) {
-        double d = 0.0;
-        for (int sweep = 0; sweep < 2; ++sweep)
-            for (int q = 0; q < m; ++q) {
-                const int i = dir == 0 ? lo + q : hi - 1 - q;
-                for (int k = rp[i]; k < rp[i + 1]; ++k)
-                    if (ci[k] == i && SSS_ABS(v[k]) > SMALLFLOAT) d = 1.e+0 / v[k];
-                (sweep == 0 ? df : dl)[dir][i] = d;
-            }
-    }
-    // level schedules: ascending (row i reads the new x_j of coupled j < i, the old x_j of j > i,
-    // which must wait for it) and descending (mirrored)
-    for (int dir = 0; dir < 2; ++dir) {
-        PassSchedule &ps = sp.pass[dir];
-        std::vector<int> depth(n, 0), pushed(n, 0);
-        auto in = [&](int j) { return j >= lo && j < hi; };
-        for (int q = 0; q < m; ++q) {
-            const int i = dir == 0 ? lo + q : hi - 1 - q;
-            int dep = pushed[i];
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = ci[k];
-                if (in(j) && (dir == 0 ? j < i : j > i)) dep = std::max(dep, depth[j] + 1);
-            }
-            depth[i] = dep;
-            for (int k = rp[i]; k < rp[i + 1]; ++k) {
-                const int j = ci[k];
-                if (in(j) && (dir == 0 ? j > i : j < i)) pushed[j] = std::max(pushed[j], dep + 1);
-            }
+    const PassSchedule &ps = sp.pass[c];
+    const bool jacobi = sp.kind == SSS_HIP_SMOOTH_JACOBI;
+    PassChoice r{PassForm::Skip, false, false};
+    if (ps.nrows == 0 || (k.pre_f && sw == 0 && c == 0)) return r;
+    r.zfirst = k.x_zero && sw == 0 && c == 0 && sp.finite && jacobi;
+    r.split = k.halo_split && !r.zfirst && !k.wave && ps.range && (!jacobi || sp.inner == 0) && !k.nocopy;
+    if (!ps.range)
+        r.form = jacobi ? PassForm::CompactJacobi : ps.compact ? PassForm::CompactExact : ps.gp.engine ? PassForm::Flow : PassForm::Depths;
+    else if (jacobi)
+        r.form = sp.inner > 0 && k.hooks ? PassForm::TwoStageHooks : k.nocopy ? PassForm::NoCopy : sp.inner > 0 ? PassForm::TwoStage
+                 : r.zfirst ? PassForm::ZeroFirst : PassForm::Jacobi;
+    else
+        r.form = k.resid && sp.fuse_resid && c == 1 && sw + 1 == k.sweeps ? PassForm::FusedResid : PassForm::Range;
+    return r;
+}
+
+struct PassRun {   // one pass as its form takes it
+    const SmootherPlan &sp;
+    const DevCSR &A;
+    const PassSchedule &ps;
+    const double *b;
+    double *x;
+    const double *deff;
+    XSrc xs;
+    hipStream_t s;
+    const PassHooks *hk;
+    bool zfirst, split;
+    int m() const { return ps.hi - ps.lo; }
+    int zgrid() const { return (m() + kBlock - 1) / kBlock; }
+};
+
+// A relaxation of the whole range pass (MODE M: 0 in place, 1 into y, 2 in place + residual): wave
+// kernels on a long-row level, else the tile path, around the halo when the pass is split.
+template <int M>
+static int relax_pass(const PassRun &p, double *y, ResidFuse *rf = nullptr)
+{
+    const DevCSR &A = p.A;
+    const PassSchedule &ps = p.ps;
+    const bool wave = A.wave_rows || A.vec_rows, tile_d = tile_diag(p.sp, A);
+    if (rf) ledger_pass(A, ps, tile_d ? 24.0 : 32.0);   // b, x and r written (and deff)
+    else ledger_pass(A, ps, (tile_d && !wave) ? 16.0 : 24.0);   // b, the written row (and deff)
+    if constexpr (M != 2)   // a long-row level never fuses the residual (SmootherPlan::fuse_resid)
+        if (wave) {
+            hipLaunchKernelGGL((A.vec_rows ? relax_range_wave<M, true> : relax_range_wave<M, false>), dim3((p.m() + 3) / 4),
+                               dim3(kBlock), 0, p.s, ps.lo, ps.hi, A.rp, A.ci, A.v, p.b, p.x, (const double *)nullptr, y,
+                               p.deff, p.xs);
+            return 0;
         }
-        int maxd = -1;
-        for (int i = lo; i < hi; ++i) maxd = std::max(maxd, depth[i]);
-        ps.depth = maxd + 1;
-        ps.h_off.assign(ps.depth + 1, 0);
-        for (int i = lo; i < hi; ++i) ps.h_off[depth[i] + 1]++;
-        for (int l = 0; l < ps.depth; ++l) ps.h_off[l + 1] += ps.h_off[l];
-        ps.nrows = m;
-        std::vector<int> fill(ps.h_off.begin(), ps.h_off.end()), rows(std::max(m, 1));
-        for (int i = lo; i < hi; ++i) rows[fill[depth[i]]++] = i;
-        if ((rc = dev_upload(ps.rows, rows, kPlanArray))) return rc;
-        if (ps.depth > 1 && (rc = gs_persist_build(ps, A, lo, hi, sp.long_rows, true, dir == 1))) return rc;
+    auto go = [&](int b0, int b1) {
+        launch_tile<M>(p.sp, A, ps, b0, b1, p.b, p.x, y, tile_d ? nullptr : p.deff, rf ? rf->r : nullptr,
+                       rf ? rf->partial : nullptr, p.xs, p.s);
+    };
+    if (p.split) return p.hk->split(p.x, ps.blo, ps.bhi, go);
+    go(ps.blo, ps.bhi);
+    return 0;
+}
+
+static int copy_rows(double *dst, const double *src, int m, hipStream_t s)
+{
+    ledger_add(16.0 * m);
+    SSS_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// zero_first_pass on the [N | L] rows (P kept) or on the level matrix's rows
+static void launch_zero_first(const PassRun &p, bool two, double *y)
+{
+    const PassSchedule &ps = p.ps;
+    if (two)
+        hipLaunchKernelGGL(zero_first_pass<true>, dim3(p.zgrid()), dim3(kBlock), 0, p.s, ps.lo, p.m(), ps.ts_nl.rp,
+                           ps.ts_nl.ci, ps.ts_nl.v, ps.ts_split, p.b, p.deff, ps.ts_P, y);
+    else
+        hipLaunchKernelGGL(zero_first_pass<false>, dim3(p.zgrid()), dim3(kBlock), 0, p.s, ps.lo, p.m(), p.A.rp, p.A.ci,
+                           p.A.v, (const int *)nullptr, p.b, p.deff, (double *)nullptr, y);
+}
+
+// iterates live in full-length work vectors whose ghosts (lower-rank rows of this class) are
+// refreshed after every stage
+static int pass_two_stage_hooks(const PassRun &p)
+{
+    const PassSchedule &ps = p.ps;
+    double *wcur = p.hk->w0, *wnxt = p.hk->w1;
+    int rc;
+    if (p.zfirst) {
+        ledger_add(32.0 * p.m());
+        launch_zero_first(p, true, wcur + ps.lo);
+    } else
+        launch_ts_stage0(ps.ts_nl, ps.lo, ps.ts_split, p.b, xsrc_of(p.x), p.deff, ps.ts_P, wcur + ps.lo, p.s);
+    for (int st = 0; st < p.sp.inner; ++st) {
+        if ((rc = p.hk->exchange(p.hk->ctx, wcur))) return rc;
+        launch_ts_inner(ps.ts_lo, ps.lo, p.deff, ps.ts_P, wcur, 0, wcur + ps.lo, wnxt + ps.lo, p.s);
+        std::swap(wcur, wnxt);
     }
-    if ((rc = dev_upload(sp.d_first, df[0], kPlanArray)) || (rc = dev_upload(sp.d_later, dl[0], kPlanArray)) ||
-        (rc = dev_upload(sp.nd_first, df[1], kPlanArray)) || (rc = dev_upload(sp.nd_later, dl[1], kPlanArray)))
+    return copy_rows(p.x + ps.lo, wcur + ps.lo, p.m(), p.s);
+}
+
+// stage 0 (or the Jacobi pass) writes the other buffer; inner steps read only this class's previous
+// iterate, so they alternate between the two buffers in place.  cur: where the class's values are.
+static int pass_nocopy(const PassRun &p, double *&cur)
+{
+    const PassSchedule &ps = p.ps;
+    const int inner = p.sp.inner;
+    double *prev = cur == p.x ? p.sp.x2 : p.x, *next = cur;
+    int rc;
+    if (p.zfirst) {
+        ledger_add((inner > 0 ? 32.0 : 24.0) * p.m());   // b, deff, y (and P)
+        launch_zero_first(p, inner > 0, prev + ps.lo);
+    } else if (inner > 0)
+        launch_ts_stage0(ps.ts_nl, ps.lo, ps.ts_split, p.b, p.xs, p.deff, ps.ts_P, prev + ps.lo, p.s);
+    else if ((rc = relax_pass<1>(p, prev + ps.lo)))
         return rc;
+    for (int st = 0; st < inner; ++st) {
+        launch_ts_inner(ps.ts_lo, ps.lo, p.deff, ps.ts_P, prev, 0, prev + ps.lo, next + ps.lo, p.s);
+        std::swap(prev, next);
+    }
+    cur = prev;
+    return 0;
+}
+
+static int pass_two_stage(const PassRun &p)
+{
+    const PassSchedule &ps = p.ps;
+    launch_ts_stage0(ps.ts_nl, ps.lo, ps.ts_split, p.b, xsrc_of(p.x), p.deff, ps.ts_P, ps.y, p.s);
+    double *ycur = ps.y, *ynxt = ps.y2;
+    for (int st = 0; st < p.sp.inner; ++st) {
+        launch_ts_inner(ps.ts_lo, ps.lo, p.deff, ps.ts_P, ycur, ps.lo, ycur, ynxt, p.s);
+        std::swap(ycur, ynxt);
+    }
+    return copy_rows(p.x + ps.lo, ycur, p.m(), p.s);
+}
+
+// the pass reads no x at all, so it may write x in place
+static int pass_zero_first(const PassRun &p)
+{
+    ledger_add(24.0 * p.m());
+    launch_zero_first(p, false, p.x + p.ps.lo);
+    return 0;
+}
+
+static int pass_jacobi(const PassRun &p)
+{
+    int rc = relax_pass<1>(p, p.ps.y);
+    return rc ? rc : copy_rows(p.x + p.ps.lo, p.ps.y, p.m(), p.s);
+}
+
+static int pass_fused_resid(const PassRun &p, ResidFuse *rf)
+{
+    int rc = relax_pass<2>(p, nullptr, rf);
+    if (!rc) rf->done = true;
+    return rc;
+}
+
+// jacobi: new values into y, then scattered; else exact, in place
+static int pass_compact(const PassRun &p, bool jacobi)
+{
+    const PassSchedule &ps = p.ps;
+    const DevCSR &S = ps.sub;
+    ledger_add((double)S.stream_bytes + (8.0 + 24.0 + (jacobi ? 20.0 : 4.0)) * ps.nrows);   // + the scatter / the row map
+    double *y = jacobi ? ps.y : nullptr;
+    const double *d = jacobi ? p.sp.d_first : p.deff;
+    if (S.wave_rows)
+        hipLaunchKernelGGL(jacobi ? relax_wave<false> : relax_wave<true>, dim3(S.ngrid), dim3(kBlock), 0, p.s, ps.nrows, S.rp,
+                           S.ci, S.v, ps.map, p.b, p.x, y, d);
+    else
+        hipLaunchKernelGGL(jacobi ? relax_compact<false> : relax_compact<true>, dim3(S.nblk), dim3(kBlock), 0, p.s, S.blk,
+                           S.rp, S.ci, S.v, ps.map, p.b, p.x, y, d);
+    if (jacobi)
+        hipLaunchKernelGGL(scatter_rows, dim3((ps.nrows + kBlock - 1) / kBlock), dim3(kBlock), 0, p.s, ps.nrows, ps.map,
+                           ps.y, p.x);
+    return 0;
+}
+
+static int pass_flow(const PassRun &p)
+{
+    ledger_pass(p.A, p.ps, 24.0);
+    return gs_persist_run(p.ps, p.A, p.b, p.x, p.deff, p.s);
+}
+
+// natural-order GS: ascending pre-smoother, descending post-smoother
+static int run_natural(const SmootherPlan &sp, const DevCSR &A, const double *b, double *x, int sweeps, hipStream_t s, bool post)
+{
+    const PassSchedule &ps = sp.pass[post ? 1 : 0];
+    if (ps.nrows == 0) return 0;
+    for (int sw = 0; sw < sweeps; ++sw) {
+        const double *deff = post ? (sw == 0 ? sp.nd_first : sp.nd_later) : (sw == 0 ? sp.d_first : sp.d_later);
+        PassRun p{sp, A, ps, b, x, deff, xsrc_of(x), s, nullptr, false, false};
+        int rc = ps.gp.engine ? pass_flow(p) : depth_launches(ps, sp.long_rows, true, A, b, x, deff, s);
+        if (rc) return rc;
+    }
     return 0;
 }
 
 int smoother_run(const SmootherPlan &sp, const DevCSR &A, const double *b, double *x, int sweeps, hipStream_t s,
                  const PassHooks *hk, ResidFuse *rf, const double *pre_f, bool x_zero, bool post)
 {
-    if (sp.natural) {   // natural-order GS: ascending pre-smoother, descending post-smoother
-        if (hk || pre_f) return ERROR_INPUT_PAR;
-        if (rf) rf->done = false;
-        const PassSchedule &ps = sp.pass[post ? 1 : 0];
-        if (ps.nrows == 0) return 0;
-        for (int sw = 0; sw < sweeps; ++sw) {
-            const double *deff = post ? (sw == 0 ? sp.nd_first : sp.nd_later) : (sw == 0 ? sp.d_first : sp.d_later);
-            if (ps.gp.engine) ledger_pass(A, ps, 24.0);
-            int rc = ps.gp.engine ? gs_persist_run(ps, A, b, x, deff, s) : depth_launches(ps, sp.long_rows, true, A, b, x, deff, s);
-            if (rc) return rc;
-        }
-        return 0;
-    }
     if (rf) rf->done = false;
+    if (sp.natural) return (hk || pre_f) ? ERROR_INPUT_PAR : run_natural(sp, A, b, x, sweeps, s, post);
     if (pre_f && (!sp.pend_ok || hk || sweeps < 1)) return ERROR_INPUT_PAR;
     if (sp.fz.engine && sweeps == sp.fz.sweeps && !hk && !pre_f) {
         for (int sw = 0; sw < sweeps; ++sw)
             for (const auto &ps : sp.pass) ledger_pass(A, ps, 24.0);
         return gs_fused_run(sp.fz, A, b, x, sp.d_first, sp.d_later, x_zero, s);
     }
-    const int n = A.n;
-    if (n == 0) return 0;
+    if (A.n == 0) return 0;
     int rc;
     // no-copy C/F-Jacobi: where each class's current values live (x or sp.x2)
     const bool nocopy = sp.x2 && !hk;
+    const PassCall call{hk != nullptr, hk && hk->split, x_zero, rf != nullptr, pre_f != nullptr, A.wave_rows || A.vec_rows,
+                        nocopy, sweeps};
     double *cur[2] = {x, x};
-    for (int sw = 0; sw < sweeps; ++sw) {
-        const double *deff = sw == 0 ? sp.d_first : sp.d_later;
+    for (int sw = 0; sw < sweeps; ++sw)
         for (int c = 0; c < 2; ++c) {
+            const PassChoice ch = pass_form(sp, c, sw, call);
+            if (ch.form == PassForm::Skip) continue;
             const PassSchedule &ps = sp.pass[c];
-            if (ps.nrows == 0) continue;
-            if (pre_f && sw == 0 && c == 0) continue;   // computed with the last residual (pre_f)
-            // first pass on a just-zeroed iterate (C/F-Jacobi / two-stage): t = b, no matrix read
-            const bool zfirst = x_zero && sw == 0 && c == 0 && sp.finite && sp.kind == SSS_HIP_SMOOTH_JACOBI;
-            // a plain tile-path relaxation pass (exact depth-1 GS-CF, or C/F-Jacobi) can overlap the
-            // halo with its interior blocks (PassHooks::split)
-            const bool fused_pass = rf && sp.fuse_resid && c == 1 && sw + 1 == sweeps;
-            const bool split_pass = hk && hk->split && !zfirst && !(A.wave_rows || A.vec_rows) && ps.range &&
-                                    (sp.kind != SSS_HIP_SMOOTH_JACOBI || sp.inner == 0) && !nocopy;
             if (hk) {   // distributed level: refresh x's ghosts; only contiguous passes qualify
                 if (!ps.range) return ERROR_INPUT_PAR;
                 // a zeroed x has zero ghosts (the descent clears own rows and ghosts); `finite` is
                 // agreed over the ranks, so every rank skips this exchange together
-                if (!zfirst && !split_pass && (rc = hk->exchange(hk->ctx, x))) return rc;
+                if (!ch.zfirst && !ch.split && (rc = hk->exchange(hk->ctx, x))) return rc;
             }
-            if (ps.range) {
-                const int nb = ps.bhi - ps.blo, m = ps.hi - ps.lo, nw = (m + 3) / 4;
-                const bool wave = A.wave_rows || A.vec_rows;
-                XSrc xs = nocopy ? XSrc{cur[0], cur[1], sp.csplit} : xsrc_of(x);
-                if (pre_f && sw == 0) xs = XSrc{pre_f, x, sp.pass[0].hi};   // this sweep's F values
-                // tile passes take each row's divisor from its staged diagonal (no deff stream)
-                const bool tile_d = sp.own_diag && (A.pk != nullptr || has_dict(A));
-                auto relax = [&](auto mode, const int *cols, const double *yp, double *y) -> int {
-                    constexpr int M = decltype(mode)::value;
-                    ledger_pass(A, ps, (tile_d && !wave) ? 16.0 : 24.0);   // b, the written row (and deff)
-                    if (wave && A.vec_rows)
-                        hipLaunchKernelGGL((relax_range_wave<M, true>), dim3(nw), dim3(kBlock), 0, s, ps.lo, ps.hi,
-                                           A.rp, cols, A.v, b, x, yp, y, deff, xs);
-                    else if (wave)
-                        hipLaunchKernelGGL((relax_range_wave<M, false>), dim3(nw), dim3(kBlock), 0, s, ps.lo, ps.hi,
-                                           A.rp, cols, A.v, b, x, yp, y, deff, xs);
-                    else {
-                        auto go = [&](int b0, int b1) {
-                            with_tile_kind(A, [&](auto K) {
-                                launch_relax_range<M, decltype(K)::value>(
-                                    b0, b1 - b0, s, devdict(A, 0), A.bk, A.rp, cols, A.v, sp.diag_pos, ps.lo, b, x, yp,
-                                    y, tile_d ? nullptr : deff, A.pk, A.pv, A.pb, (double *)nullptr, (double *)nullptr,
-                                    xs);
-                            });
-                        };
-                        if (split_pass) return hk->split(x, ps.blo, ps.bhi, go);
-                        go(ps.blo, ps.bhi);
-                    }
-                    return 0;
-                };
-                (void)nb;
-                if (sp.kind == SSS_HIP_SMOOTH_JACOBI && sp.inner > 0 && hk) {
-                    // iterates live in full-length work vectors whose ghosts (lower-rank rows of
-                    // this class) are refreshed after every stage
-                    const DevCSR &Mn = ps.ts_nl, &Ml = ps.ts_lo;
-                    double *wcur = hk->w0, *wnxt = hk->w1;
-                    if (zfirst) {
-                        ledger_add(32.0 * m);
-                        hipLaunchKernelGGL(zero_first_pass<true>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                                           ps.lo, m, Mn.rp, Mn.ci, Mn.v, ps.ts_split, b, deff, ps.ts_P, wcur + ps.lo);
-                    } else
-                        launch_ts_stage0(Mn, ps.lo, ps.ts_split, b, xsrc_of(x), deff, ps.ts_P, wcur + ps.lo, s);
-                    for (int st = 0; st < sp.inner; ++st) {
-                        if ((rc = hk->exchange(hk->ctx, wcur))) return rc;
-                        launch_ts_inner(Ml, ps.lo, deff, ps.ts_P, wcur, 0, wcur + ps.lo, wnxt + ps.lo, s);
-                        std::swap(wcur, wnxt);
-                    }
-                    ledger_add(16.0 * m);
-                    SSS_HIP(hipMemcpyAsync(x + ps.lo, wcur + ps.lo, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice,
-                                           s));
-                } else if (sp.kind == SSS_HIP_SMOOTH_JACOBI && nocopy) {
-                    // stage 0 (or the Jacobi pass) writes the other buffer; inner steps read only this
-                    // class's previous iterate, so they alternate between the two buffers in place
-                    double *prev = cur[c] == x ? sp.x2 : x, *next = cur[c];
-                    const int zg = (m + kBlock - 1) / kBlock;
-                    if (zfirst) ledger_add((sp.inner > 0 ? 32.0 : 24.0) * m);   // b, deff, y (and P)
-                    if (zfirst && sp.inner > 0)
-                        hipLaunchKernelGGL(zero_first_pass<true>, dim3(zg), dim3(kBlock), 0, s, ps.lo, m, ps.ts_nl.rp,
-                                           ps.ts_nl.ci, ps.ts_nl.v, ps.ts_split, b, deff, ps.ts_P, prev + ps.lo);
-                    else if (zfirst)
-                        hipLaunchKernelGGL(zero_first_pass<false>, dim3(zg), dim3(kBlock), 0, s, ps.lo, m, A.rp, A.ci,
-                                           A.v, (const int *)nullptr, b, deff, (double *)nullptr, prev + ps.lo);
-                    else if (sp.inner > 0)
-                        launch_ts_stage0(ps.ts_nl, ps.lo, ps.ts_split, b, xs, deff, ps.ts_P, prev + ps.lo, s);
-                    else if ((rc = relax(std::integral_constant<int, 1>(), A.ci, (const double *)nullptr, prev + ps.lo)))
-                        return rc;
-                    for (int st = 0; st < sp.inner; ++st) {
-                        launch_ts_inner(ps.ts_lo, ps.lo, deff, ps.ts_P, prev, 0, prev + ps.lo, next + ps.lo, s);
-                        std::swap(prev, next);
-                    }
-                    cur[c] = prev;
-                } else if (sp.kind == SSS_HIP_SMOOTH_JACOBI && sp.inner > 0) {
-                    const DevCSR &Mn = ps.ts_nl, &Ml = ps.ts_lo;
-                    launch_ts_stage0(Mn, ps.lo, ps.ts_split, b, xsrc_of(x), deff, ps.ts_P, ps.y, s);
-                    double *ycur = ps.y, *ynxt = ps.y2;
-                    for (int st = 0; st < sp.inner; ++st) {
-                        launch_ts_inner(Ml, ps.lo, deff, ps.ts_P, ycur, ps.lo, ycur, ynxt, s);
-                        std::swap(ycur, ynxt);
-                    }
-                    ledger_add(16.0 * m);
-                    SSS_HIP(hipMemcpyAsync(x + ps.lo, ycur, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
-                } else if (sp.kind == SSS_HIP_SMOOTH_JACOBI && zfirst) {
-                    // the pass reads no x at all, so it may write x in place
-                    ledger_add(24.0 * m);
-                    hipLaunchKernelGGL(zero_first_pass<false>, dim3((m + kBlock - 1) / kBlock), dim3(kBlock), 0, s,
-                                       ps.lo, m, A.rp, A.ci, A.v, (const int *)nullptr, b, deff, (double *)nullptr,
-                                       x + ps.lo);
-                } else if (sp.kind == SSS_HIP_SMOOTH_JACOBI) {
-                    if ((rc = relax(std::integral_constant<int, 1>(), A.ci, (const double *)nullptr, ps.y))) return rc;
-                    ledger_add(16.0 * m);
-                    SSS_HIP(hipMemcpyAsync(x + ps.lo, ps.y, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
-                } else if (fused_pass) {
-                    ledger_pass(A, ps, tile_d ? 24.0 : 32.0);   // b, x and r written (and deff)
-                    auto go = [&](int b0, int b1) {
-                        with_tile_kind(A, [&](auto K) {
-                            launch_relax_range<2, decltype(K)::value>(
-                                b0, b1 - b0, s, devdict(A, 0), A.bk, A.rp, A.ci, A.v, sp.diag_pos, ps.lo, b, x,
-                                (const double *)nullptr, (double *)nullptr, tile_d ? nullptr : deff, A.pk, A.pv, A.pb,
-                                rf->r, rf->partial, xs);
-                        });
-                    };
-                    if (split_pass) {
-                        if ((rc = hk->split(x, ps.blo, ps.bhi, go))) return rc;
-                    } else {
-                        go(ps.blo, ps.bhi);
-                    }
-                    rf->done = true;
-                } else if ((rc = relax(std::integral_constant<int, 0>(), A.ci, (const double *)nullptr, (double *)nullptr))) {
-                    return rc;
-                }
-                if (pre_f && sw == 0 && c == 1 && sweeps == 1) {   // no later F pass overwrites x_F
-                    ledger_add(16.0 * sp.pass[0].hi);
-                    SSS_HIP(hipMemcpyAsync(x, pre_f, sizeof(double) * (size_t)sp.pass[0].hi, hipMemcpyDeviceToDevice, s));
-                }
-                continue;
+            XSrc xs = nocopy ? XSrc{cur[0], cur[1], sp.csplit} : xsrc_of(x);
+            if (pre_f && sw == 0) xs = XSrc{pre_f, x, sp.pass[0].hi};   // this sweep's F values
+            const PassRun p{sp, A, ps, b, x, sw == 0 ? sp.d_first : sp.d_later, xs, s, hk, ch.zfirst, ch.split};
+            switch (ch.form) {
+            case PassForm::TwoStageHooks: rc = pass_two_stage_hooks(p); break;
+            case PassForm::NoCopy: rc = pass_nocopy(p, cur[c]); break;
+            case PassForm::TwoStage: rc = pass_two_stage(p); break;
+            case PassForm::ZeroFirst: rc = pass_zero_first(p); break;
+            case PassForm::Jacobi: rc = pass_jacobi(p); break;
+            case PassForm::FusedResid: rc = pass_fused_resid(p, rf); break;
+            case PassForm::Range: rc = relax_pass<0>(p, nullptr); break;
+            case PassForm::CompactJacobi: rc = pass_compact(p, true); break;
+            case PassForm::CompactExact: rc = pass_compact(p, false); break;
+            case PassForm::Flow: rc = pass_flow(p); break;
+            default: rc = depth_launches(ps, sp.long_rows, false, A, b, x, p.deff, s); break;
             }
-            if (sp.kind == SSS_HIP_SMOOTH_JACOBI) {
-                ledger_add((double)ps.sub.stream_bytes + (8.0 + 24.0 + 20.0) * ps.nrows);   // + the scatter
-                if (ps.sub.wave_rows)
-                    hipLaunchKernelGGL(relax_wave<false>, dim3(ps.sub.ngrid), dim3(kBlock), 0, s, ps.nrows, ps.sub.rp,
-                                       ps.sub.ci, ps.sub.v, ps.map, b, x, ps.y, sp.d_first);
-                else
-                    hipLaunchKernelGGL(relax_compact<false>, dim3(ps.sub.nblk), dim3(kBlock), 0, s, ps.sub.blk,
-                                       ps.sub.rp, ps.sub.ci, ps.sub.v, ps.map, b, x, ps.y, sp.d_first);
-                hipLaunchKernelGGL(scatter_rows, dim3((ps.nrows + kBlock - 1) / kBlock), dim3(kBlock), 0, s, ps.nrows,
-                                   ps.map, ps.y, x);
-                continue;
-            }
-            if (ps.compact) {
-                ledger_add((double)ps.sub.stream_bytes + (8.0 + 24.0 + 4.0) * ps.nrows);   // + the row map
-                if (ps.sub.wave_rows)
-                    hipLaunchKernelGGL(relax_wave<true>, dim3(ps.sub.ngrid), dim3(kBlock), 0, s, ps.nrows, ps.sub.rp,
-                                       ps.sub.ci, ps.sub.v, ps.map, b, x, (double *)nullptr, deff);
-                else
-                    hipLaunchKernelGGL(relax_compact<true>, dim3(ps.sub.nblk), dim3(kBlock), 0, s, ps.sub.blk,
-                                       ps.sub.rp, ps.sub.ci, ps.sub.v, ps.map, b, x, (double *)nullptr, deff);
-                continue;
-            }
-            if (ps.gp.engine) {
-                ledger_pass(A, ps, 24.0);
-                if ((rc = gs_persist_run(ps, A, b, x, deff, s))) return rc;
-                continue;
-            }
-            if ((rc = depth_launches(ps, sp.long_rows, false, A, b, x, deff, s))) return rc;
+            if (rc) return rc;
+            // the F values came with the last residual and no later F pass overwrites x_F
+            if (ps.range && pre_f && sw == 0 && c == 1 && sweeps == 1 && (rc = copy_rows(x, pre_f, sp.pass[0].hi, s)))
+                return rc;
         }
-    }
     for (int c = 0; c < 2; ++c)   // odd number of writes to a class (odd sweeps x (1 + inner))
-        if (cur[c] != x) {
-            ledger_add(16.0 * (sp.pass[c].hi - sp.pass[c].lo));
-            SSS_HIP(hipMemcpyAsync(x + sp.pass[c].lo, cur[c] + sp.pass[c].lo,
-                                   sizeof(double) * (size_t)(sp.pass[c].hi - sp.pass[c].lo), hipMemcpyDeviceToDevice, s));
-        }
+        if (cur[c] != x && (rc = copy_rows(x + sp.pass[c].lo, cur[c] + sp.pass[c].lo, sp.pass[c].hi - sp.pass[c].lo, s)))
+            return rc;
     SSS_HIP(hipGetLastError());
     return 0;
 }

@@ -1,6 +1,7 @@
 # Storage of each level of a hierarchy on the GPU: the formats (sss_hip_level_info a_format / r_format /
 # p_format bits), the bytes one SpMV streams of A_l (a_stream_bytes) and the level's slot of the byte
-# ledger (sss_hip_cycle_bytes); then the ledger's outer-residual and coarse-solve slots.
+# ledger (sss_hip_cycle_bytes); then the ledger's outer-residual and coarse-solve slots, and the kernels
+# of one captured cycle (sss_hip_cycle_launches, after one cycle from b = x = 1).
 #   python tools/fmt_probe.py 64               7-pt 64^3
 #   python tools/fmt_probe.py 27:16            27-pt 16^3
 #   python tools/fmt_probe.py bus              tests/golden/1138_bus.mtx
@@ -29,3 +30,7 @@ cb = D.cycle_bytes()
 for l in range(H.num_levels - 1):
     i = D.level_info(l); print(l, i.a_format, i.r_format, i.p_format, i.a_stream_bytes, int(cb["levels"][l]))
 print("outer", int(cb["outer"]), "coarse", int(cb["coarse"]))
+import numpy as np
+D.upload(0, "b", np.ones(M.num_rows)); D.upload(0, "x", np.ones(M.num_rows))
+D.cycle()   # captures the cycle: sss_hip_cycle_launches counts the kernels of the captured graph
+print("launches", A.lib().sss_hip_cycle_launches(D.h))
