@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "SSS_amg_pars_init", "SSS_amg_pars_print", "mmio_info", "mmio_data",
     "sss_hip_opts_default", "sss_hip_device_count", "sss_hip_mem_info", "sss_hip_hier_create", "sss_hip_hier_destroy",
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
+    "sss_hip_rap_values", "sss_rap_values_host", "SSS_amg_refresh", "sss_hip_hier_refresh",
     "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
@@ -190,6 +191,10 @@ def _declare(lib):
                                               P(C.c_double)]),
         "sss_hip_hier_destroy": (None, [C.c_void_p]),
         "sss_hip_rap": (C.c_int, [P(SSS_MAT), P(SSS_MAT), P(SSS_MAT), P(SSS_MAT)]),
+        "sss_hip_rap_values": (C.c_int, [P(SSS_MAT), P(SSS_MAT), P(SSS_MAT), P(SSS_MAT)]),
+        "sss_rap_values_host": (C.c_int, [P(SSS_MAT), P(SSS_MAT), P(SSS_MAT), P(SSS_MAT)]),
+        "SSS_amg_refresh": (C.c_int, [P(SSS_AMG), P(SSS_MAT)]),
+        "sss_hip_hier_refresh": (C.c_int, [C.c_void_p, P(SSS_AMG)]),
         "sss_hip_pmis": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
         "sss_pmis_host": (C.c_int, [P(SSS_IMAT), _int_p, _int_p, _int_p]),
         "sss_hip_std_pattern": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
@@ -343,6 +348,19 @@ def pmis(rp, ci, device: bool = False):
     return mark[:n], nc.value, rounds.value
 
 
+def rap_values(R: SSS_MAT, A: SSS_MAT, P: SSS_MAT, C_: SSS_MAT, device: bool = False) -> None:
+    """The values of the Galerkin product R A P written into C_.val, on the pattern C_ already has
+    (row_ptr, col_idx of SSS_blas_mat_rap for operators with these patterns): bit for bit that
+    product's values, on the host (sss_rap_values_host) or on the GPU (sss_hip_rap_values).  Raises
+    RuntimeError with the error code (.rc) when it fails; C_.val is then untouched."""
+    fn = lib().sss_hip_rap_values if device else lib().sss_rap_values_host
+    rc = fn(C.byref(R), C.byref(A), C.byref(P), C.byref(C_))
+    if rc != 0:
+        err = RuntimeError(f"rap_values failed ({rc})")
+        err.rc = rc
+        raise err
+
+
 def _imat(rp, ci):
     rp = np.ascontiguousarray(rp, dtype=np.int32)
     ci = np.ascontiguousarray(ci, dtype=np.int32)
@@ -443,6 +461,16 @@ class Hierarchy:
             raise OSError(f"SSS_amg_load({path}) failed ({rc})")
         H.pars = H.mg.pars
         return H
+
+    def refresh(self, A: SSS_MAT) -> None:
+        """New operator values on the same pattern (SSS_amg_refresh): C/F marks, P and R stay, the
+        coarse operators are recomputed from A.  Raises ValueError when A's pattern is not level 0's
+        (the hierarchy is then untouched), RuntimeError on any other failure."""
+        rc = lib().SSS_amg_refresh(C.byref(self.mg), C.byref(A))
+        if rc == -12:   # ERROR_INPUT_PAR
+            raise ValueError("refresh: the operator does not have the pattern of the hierarchy's level 0")
+        if rc != 0:
+            raise RuntimeError(f"SSS_amg_refresh failed ({rc})")
 
     @property
     def num_levels(self) -> int:
@@ -548,6 +576,12 @@ class DeviceHierarchy:
         self._check(lib().sss_hip_fgmres(self.h, tol, restart, maxit, C.byref(its), C.byref(rel), dptr(hist), len(hist)),
                     "fgmres")
         return its.value, hist[: its.value].copy()
+
+    def refresh(self):
+        """Follow self.H after Hierarchy.refresh (sss_hip_hier_refresh): the operators, smoother
+        plans, coarse solver, tail and graphs are rebuilt; vectors, P and R are kept.  After a failure
+        the mirror can only be closed."""
+        self._check(lib().sss_hip_hier_refresh(self.h, C.byref(self.H.mg)), "refresh")
 
     def smooth(self, level: int, post: bool):
         self._check(lib().sss_hip_smooth(self.h, level, int(post)), "smooth")

@@ -34,6 +34,7 @@ struct sss_hip_hier {
     int nl = 0;
     SSS_AMG_PARS pars{};
     sss_hip_opts opts{};
+    int use_graph_req = 0;   // opts.use_graph as asked for (opts.use_graph: as decided from the plans)
     hipStream_t stream = nullptr;
     struct Level {
         DevCSR A, P, R;
@@ -356,6 +357,7 @@ static bool hb_begin(HierBuild &b, const SSS_AMG *mg, const sss_hip_opts *o, int
     h->pars = mg->pars;
     if (o) h->opts = *o;
     else sss_hip_opts_default(&h->opts);
+    h->use_graph_req = h->opts.use_graph;
     if (h->opts.device >= 0 && hipSetDevice(h->opts.device) != hipSuccess) return hb_fail(b, "device");
     h->level_base = level_base;
     if (stream) {
@@ -401,7 +403,7 @@ static void hb_perm(HierBuild &b, int l)
     });
 }
 
-// A_l (+ its smoother plan unless coarsest) and the level vectors
+// A_l (+ its smoother plan unless coarsest) and the level vectors (a refresh keeps the ones it has)
 static bool hb_level_a(HierBuild &b, int l, bool coarsest)
 {
     TraceRange tr("mirror level %d: A + smoother plan", l);
@@ -450,6 +452,7 @@ static bool hb_level_a(HierBuild &b, int l, bool coarsest)
     if (b.timing)
         fprintf(stderr, "[sss_hip] upload level %d: relabel %.2f s, A %.2f s, smoother plan %.2f s\n", l,
                 rl ? t_rel - t_a : 0.0, rl ? t_up - t_rel : t_sm - t_a, rl ? t_sm - t_up : 0.0);
+    if (L.b && L.x && L.wp) return true;
     L.b = dev_alloc<double>((size_t)n);
     L.x = dev_alloc<double>((size_t)n);
     L.wp = dev_alloc<double>((size_t)n);
@@ -599,26 +602,25 @@ static int tail_build(sss_hip_hier *h, const SSS_AMG *mg)
     return 0;
 }
 
-static sss_hip_hier *hb_finish(HierBuild &b)
+// What the mirror holds beyond its levels and depends on their operators: the norm's partials, the
+// pending-F buffer, the coarse solver, the single-workgroup tail, the graph decision.  Runs at the
+// end of the construction and of a refresh (which has released the previous ones).  nullptr, or
+// what failed.
+static const char *hier_finalize(sss_hip_hier *h, const SSS_AMG *mg)
 {
-    sss_hip_hier *h = b.h;
-    const SSS_AMG *mg = b.mg;
-    auto fail = [&](const char *what) {
-        fprintf(stderr, "### ERROR: sss_hip_hier_create: %s\n", what);
-        hier_release(h);
-        b.h = nullptr;
-        return (sss_hip_hier *)nullptr;
-    };
-    if (b.err) return fail(b.err);
+    auto fail = [](const char *what) { return what; };
     h->partial = dev_alloc<double>((size_t)h->L[0].A.ngrid + kFinalScratch);
     if (h->nl > 1 && h->L[0].sm.pend_ok) {
         h->pend_f = dev_alloc<double>((size_t)std::max(h->L[0].sm.pass[0].hi, 1));
         if (!h->pend_f) return fail("pending F pass buffer");
     }
-    h->d_norm = dev_alloc<double>(2);
-    h->d_err = dev_alloc<unsigned>(1);
-    if (!h->partial || !h->d_norm || !h->d_err || hipHostMalloc((void **)&h->h_norm, 2 * sizeof(double)) != hipSuccess)
-        return fail("norm buffers");
+    if (!h->d_norm) {
+        h->d_norm = dev_alloc<double>(2);
+        h->d_err = dev_alloc<unsigned>(1);
+        if (!h->d_norm || !h->d_err || hipHostMalloc((void **)&h->h_norm, 2 * sizeof(double)) != hipSuccess)
+            return fail("norm buffers");
+    }
+    if (!h->partial) return fail("norm buffers");
     if (hipMemset(h->d_err, 0, sizeof(unsigned)) != hipSuccess || hipMemset(h->d_norm, 0, 2 * sizeof(double)) != hipSuccess)
         return fail("norm buffers");
     for (int l = 0; l + 1 < h->nl; ++l) smoother_set_err(h->L[l].sm, h->d_err);
@@ -657,15 +659,112 @@ static sss_hip_hier *hb_finish(HierBuild &b)
                          : ps.gp.engine ? 1 : ps.depth;
         launches += per_sweep * (h->pars.pre_iter + h->pars.post_iter) + 4;
     }
-    if (launches > 4096) h->opts.use_graph = 0;
+    h->opts.use_graph = launches > 4096 ? 0 : h->use_graph_req;
     if (h->opts.verbose) {
         for (int l = 0; l < h->nl; ++l)
             fprintf(stderr, "[sss_hip] level %d: n=%d nnz=%d blocks=%d dagF=%d dagC=%d kind=%d gs engine F/C=%d/%d\n", l,
                     h->L[l].A.n, h->L[l].A.nnz, h->L[l].A.nblk, h->L[l].sm.pass[0].depth, h->L[l].sm.pass[1].depth,
                     h->L[l].sm.kind, h->L[l].sm.pass[0].gp.engine, h->L[l].sm.pass[1].gp.engine);
     }
+    return nullptr;
+}
+
+static sss_hip_hier *hb_finish(HierBuild &b)
+{
+    sss_hip_hier *h = b.h;
+    const char *what = b.err ? b.err.load() : hier_finalize(h, b.mg);
     b.h = nullptr;
+    if (what) {
+        fprintf(stderr, "### ERROR: sss_hip_hier_create: %s\n", what);
+        hier_release(h);
+        return nullptr;
+    }
     return h;
+}
+
+static void destroy_graphs(sss_hip_hier *h)
+{
+    for (auto *steps : {&h->cycle_steps, &h->cycle_steps_p}) {
+        for (hipGraphExec_t g : *steps)
+            if (g) (void)hipGraphExecDestroy(g);
+        steps->clear();
+    }
+    if (h->resid_exec) (void)hipGraphExecDestroy(h->resid_exec);
+    if (h->resid_f_exec) (void)hipGraphExecDestroy(h->resid_f_exec);
+    h->resid_exec = h->resid_f_exec = nullptr;
+    h->cycle_graph_ready = h->cycle_graph_ready_p = false;
+    h->cycle_kernels = h->cycle_kernels_p = 0;
+}
+
+// The mirror after SSS_amg_refresh (include/sss_hip.h): every level's A, with its smoother plan,
+// from the new values; what hier_finalize builds; the graphs are captured again at their next use.
+// The level tasks are independent and run side by side as in hier_create_impl.
+extern "C" int sss_hip_hier_refresh(sss_hip_hier *h, const SSS_AMG *mg)
+{
+    if (!h || !mg || !mg->cg || mg->num_levels != h->nl || h->nl < 1) return ERROR_INPUT_PAR;
+    const int nl = h->nl;
+    for (int l = 0; l < nl; ++l)
+        if (mg->cg[l].A.num_rows != h->L[l].A.n || mg->cg[l].A.num_nnzs != h->L[l].A.nnz) return ERROR_INPUT_PAR;
+    if (h->opts.device >= 0) SSS_HIP(hipSetDevice(h->opts.device));
+    SSS_HIP(hipStreamSynchronize(h->stream));
+    destroy_graphs(h);
+    h->resid_c_ready = h->pending_f = false;
+    tail_free(h->tail);
+    coarse_direct_free(h->direct);
+    coarse_krylov_destroy(h->krylov);
+    h->krylov = nullptr;
+    dev_free(h->partial);
+    dev_free(h->pend_f);
+    h->partial = h->pend_f = nullptr;
+    HierBuild b;
+    b.h = h;
+    b.mg = mg;
+    for (int l = 0; l + 1 < nl; ++l) {   // what hb_perm left beside the relabeling itself
+        const auto &perm = h->L[l].perm;
+        if (perm.empty()) continue;
+        const int n = (int)perm.size();
+        const int *cf = mg->cg[l].cfmark.d;
+        b.inv[l].resize((size_t)n);
+        int nF = 0;
+        for (int i = 0; i < n; ++i) {
+            b.inv[l][(size_t)perm[i]] = i;
+            nF += cf[i] != 1;
+        }
+        b.nF[l] = nF;
+    }
+    int device = 0;
+    (void)hipGetDevice(&device);
+    std::atomic<int> next{0};
+    auto work = [&] {
+        for (int l; (l = next++) < nl && !b.err;) {
+            auto &L = h->L[l];
+            const bool f_over = L.sm.f_overwritten;
+            devcsr_free(L.A);
+            smoother_free(L.sm);
+            if (!hb_level_a(b, l, l + 1 == nl) || l + 1 == nl) continue;
+            if (L.sm.f_overwritten != f_over) {   // decides P's encoding and the injection list
+                devcsr_free(L.P);
+                devcsr_free(L.R);
+                dev_free(L.pinj);
+                L.pinj = nullptr;
+                hb_level_pr(b, l);
+            }
+        }
+    };
+    std::vector<std::thread> helpers;
+    for (int k = 0; k < std::min(5, nl - 1); ++k)
+        helpers.emplace_back([&] {
+            (void)hipSetDevice(device);
+            work();
+        });
+    work();
+    for (auto &t : helpers) t.join();
+    const char *what = b.err ? b.err.load() : hier_finalize(h, mg);
+    if (what) {
+        fprintf(stderr, "### ERROR: sss_hip_hier_refresh: %s\n", what);
+        return ERROR_MISC;
+    }
+    return 0;
 }
 
 

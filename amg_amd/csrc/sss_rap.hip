@@ -155,6 +155,124 @@ __global__ __launch_bounds__(G * RPB) void rap_rows(int nrows, const int *__rest
     }
 }
 
+// sss_hip_rap_values: the same walk on a row whose pattern is known.  The row's column -> slot
+// table is filled from the row of C itself (a column's slot is its position in the row), the
+// diagonal's slot starts at 0.0 and every other one at -0.0, and every product adds: x + -0.0 is x
+// for every x (-0.0 included), so the first product of a slot lands as the reference's assignment
+// does.  One pass, no slot counting.  flag bits: 1 a product's column is absent from the row of C,
+// 2 an index out of range or a row of C that does not start with its diagonal / repeats a column.
+template <int G, int VS, int RPB>
+__global__ __launch_bounds__(G * RPB) void rap_rows_values(int nrows, const int *__restrict__ list, int nc, int nf, int np,
+                                                       const int *__restrict__ rrp, const int *__restrict__ rci,
+                                                       const double *__restrict__ rv, const int *__restrict__ arp,
+                                                       const int *__restrict__ aci, const double *__restrict__ av,
+                                                       const int *__restrict__ prp, const int *__restrict__ pci,
+                                                       const double *__restrict__ pv, const int *__restrict__ crp,
+                                                       const int *__restrict__ cci, double *__restrict__ cval,
+                                                       unsigned *__restrict__ flag)
+{
+    constexpr int HS = 2 * VS;
+    __shared__ unsigned hkey[RPB][HS];
+    __shared__ int hslot[RPB][HS];
+    __shared__ double sval[RPB][VS];
+    const int lane = threadIdx.x & 63, g = threadIdx.x / G, gl = threadIdx.x % G;
+    const int gbase = lane - gl;   // first lane of this row's group within the wave
+    const int t = blockIdx.x * RPB + g;
+    const bool live = t < nrows;
+    const int ic = live ? list[t] : 0;
+    unsigned *hk = hkey[g];
+    int *hs = hslot[g];
+    for (int k = gl; k < HS; k += G) hk[k] = kEmpty;
+    __syncthreads();
+    if (!live || ic < 0 || ic >= nc) {
+        if (live && gl == 0) atomicOr(flag, 2u);
+        return;
+    }
+    const int c0 = crp[ic];
+    const int len = crp[ic + 1] - c0;
+    if (len < 1 || len > VS || cci[c0] != ic) {   // (the host sorted the rows by length: never too long)
+        if (gl == 0) atomicOr(flag, 2u);
+        return;
+    }
+    unsigned bad = 0;
+    for (int k = gl; k < len; k += G) {
+        const int c = cci[c0 + k];
+        sval[g][k] = k == 0 ? 0.0 : -0.0;
+        if (c < 0 || c >= nc) {
+            bad |= 2u;
+            continue;
+        }
+        unsigned h = rap_hash((unsigned)c, HS);
+        for (;;) {   // at most VS keys in 2 VS buckets: an empty one is always reached
+            const unsigned old = atomicCAS(&hk[h], kEmpty, (unsigned)c);
+            if (old == kEmpty) {
+                hs[h] = k;
+                break;
+            }
+            if (old == (unsigned)c) {   // a column twice in the row
+                bad |= 2u;
+                break;
+            }
+            h = (h + 1) & (HS - 1);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int q1 = rrp[ic]; q1 < rrp[ic + 1]; ++q1) {
+        const double r = rv[q1];
+        const int i1 = rci[q1];
+        if (i1 < 0 || i1 >= nf) {   // (uniform over the group)
+            bad |= 2u;
+            continue;
+        }
+        const int a0 = arp[i1], a1 = arp[i1 + 1];
+        for (int ab = a0; ab < a1; ab += G) {
+            // this chunk's A entries and their P row bounds, one per lane
+            int p0 = 0, p1 = 0;
+            double a = 0.0;
+            if (ab + gl < a1) {
+                const int i2 = aci[ab + gl];
+                a = av[ab + gl];
+                if (i2 < 0 || i2 >= np) bad |= 2u;   // (p0 == p1: the entry is skipped)
+                else p0 = prp[i2], p1 = prp[i2 + 1];
+            }
+            const int ne = min(G, a1 - ab);
+            for (int e = 0; e < ne; ++e) {
+                const double ae = __shfl(a, gbase + e, 64);
+                const int e0 = __shfl(p0, gbase + e, 64), e1 = __shfl(p1, gbase + e, 64);
+                const double ra = r * ae;
+                for (int pb = e0; pb < e1; pb += G) {
+                    const int q3 = pb + gl;
+                    if (q3 < e1) {
+                        const unsigned col = (unsigned)pci[q3];
+                        const double rap = ra * pv[q3];
+                        int slot = -1;
+                        unsigned h = rap_hash(col, HS);
+                        for (;;) {
+                            const unsigned k = hk[h];
+                            if (k == col) {
+                                slot = hs[h];
+                                break;
+                            }
+                            if (k == kEmpty) break;
+                            h = (h + 1) & (HS - 1);
+                        }
+                        // the columns of one P row are distinct: no slot is touched twice in a step
+                        if (slot >= 0) sval[g][slot] += rap;
+                        else bad |= 1u;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                }
+            }
+        }
+    }
+    if (bad) atomicOr(flag, bad);
+    for (int k = gl; k < len; k += G) cval[c0 + k] = sval[g][k];
+}
+
 struct DevMat {
     int *rp = nullptr, *ci = nullptr;
     double *v = nullptr;
@@ -237,6 +355,75 @@ int copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind k, hipStre
     return 0;
 }
 constexpr int kCfgs = 4;
+constexpr int kCfgSlots[kCfgs] = {32, 128, 512, 4096};   // VS of launch_cfg's configurations
+
+template <int G, int VS, int RPB>
+void launch_values(int nrows, const int *list, const SSS_MAT &Ch, const DevMat &R, const DevMat &A, const DevMat &P,
+                   const int *crp, const int *cci, double *cval, unsigned *flag, int nf, int np, hipStream_t st)
+{
+    if (nrows <= 0) return;
+    hipLaunchKernelGGL((rap_rows_values<G, VS, RPB>), dim3((nrows + RPB - 1) / RPB), dim3(G * RPB), 0, st, nrows, list,
+                       Ch.num_rows, nf, np, R.rp, R.ci, R.v, A.rp, A.ci, A.v, P.rp, P.ci, P.v, crp, cci, cval, flag);
+}
+void launch_values_cfg(int c, int nrows, const int *list, const SSS_MAT &Ch, const DevMat &R, const DevMat &A,
+                       const DevMat &P, const int *crp, const int *cci, double *cval, unsigned *flag, int nf, int np,
+                       hipStream_t st)
+{
+    switch (c) {
+    case 0: launch_values<8, 32, 32>(nrows, list, Ch, R, A, P, crp, cci, cval, flag, nf, np, st); break;
+    case 1: launch_values<16, 128, 16>(nrows, list, Ch, R, A, P, crp, cci, cval, flag, nf, np, st); break;
+    case 2: launch_values<64, 512, 4>(nrows, list, Ch, R, A, P, crp, cci, cval, flag, nf, np, st); break;
+    default: launch_values<64, 4096, 1>(nrows, list, Ch, R, A, P, crp, cci, cval, flag, nf, np, st); break;
+    }
+}
+
+// the values of one coarse row on the host (sss_rap_values_host's walk, sss_setup.c), for the rows
+// longer than the largest device table: out[0 .. row length).  mark/slot: nc ints, mark[] != ic
+// on entry.  false: an index out of range or a product whose column the row of C does not hold.
+bool host_row_values(int ic, const SSS_MAT &R, const SSS_MAT &A, const SSS_MAT &P, const SSS_MAT &C, int *mark, int *slot,
+                     double *out)
+{
+    const int nc = C.num_rows, c0 = C.row_ptr[ic], len = C.row_ptr[ic + 1] - c0;
+    if (len < 1 || C.col_idx[c0] != ic) return false;
+    for (int k = 0; k < len; ++k) {
+        const int c = C.col_idx[c0 + k];
+        if (c < 0 || c >= nc || mark[c] == ic) return false;
+        mark[c] = ic;
+        slot[c] = k;
+        out[k] = k == 0 ? 0.0 : -0.0;
+    }
+    for (int q1 = R.row_ptr[ic]; q1 < R.row_ptr[ic + 1]; ++q1) {
+        const double r = R.val[q1];
+        const int i1 = R.col_idx[q1];
+        if (i1 < 0 || i1 >= A.num_rows) return false;
+        for (int q2 = A.row_ptr[i1]; q2 < A.row_ptr[i1 + 1]; ++q2) {
+            const double ra = r * A.val[q2];
+            const int i2 = A.col_idx[q2];
+            if (i2 < 0 || i2 >= P.num_rows) return false;
+            for (int q3 = P.row_ptr[i2]; q3 < P.row_ptr[i2 + 1]; ++q3) {
+                const int i3 = P.col_idx[q3];
+                if (i3 < 0 || i3 >= nc || mark[i3] != ic) return false;
+                out[slot[i3]] += ra * P.val[q3];
+            }
+        }
+    }
+    return true;
+}
+
+// row pointers of an n-row matrix with nnz entries: 0 first, nnz last, never falling
+bool row_ptr_ok(const SSS_MAT &M)
+{
+    if (M.num_rows < 0 || M.num_nnzs < 0 || !M.row_ptr || M.row_ptr[0] != 0 || M.row_ptr[M.num_rows] != M.num_nnzs) return false;
+    std::atomic<int> ok{1};
+    parallel_chunks(M.num_rows, 1 << 16, [&](int lo, int hi) {
+        for (int i = lo; i < hi; ++i)
+            if (M.row_ptr[i + 1] < M.row_ptr[i]) ok = 0;
+    });
+    return ok != 0;
+}
+
+// seconds this thread's last product spent in copies (with allocations) and in kernels
+thread_local double g_rap_times[2] = {0.0, 0.0};
 
 }  // namespace
 
@@ -261,7 +448,9 @@ extern "C" int sss_hip_rap(const SSS_MAT *Rh, const SSS_MAT *Ah, const SSS_MAT *
     if (hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
     hipStream_t st = stream.s;
     DevMat R, A, P;
+    const double t_begin = PhaseTimer::now();
     if (R.up(*Rh) || A.up(*Ah) || P.up(*Ph)) return ERROR_MISC;
+    const double t_up = PhaseTimer::now();   // (sss_hip_rap_times: uploads and downloads against the rest)
     int *cnt = dev_alloc<int>((size_t)std::max(nc, 1));
     int *list = dev_alloc<int>((size_t)std::max(nc, 1));
     if (!cnt || !list) {
@@ -352,6 +541,7 @@ extern "C" int sss_hip_rap(const SSS_MAT *Rh, const SSS_MAT *Ah, const SSS_MAT *
         if (hipGetLastError() != hipSuccess) rc = ERROR_MISC;
     }
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = ERROR_MISC;
+    const double t_kern = PhaseTimer::now();
     if (!rc) {
         const int nnz = (int)start[nc];
         C->num_rows = nc;
@@ -372,5 +562,124 @@ extern "C" int sss_hip_rap(const SSS_MAT *Rh, const SSS_MAT *Ah, const SSS_MAT *
     dev_free(d_start);
     dev_free(d_ci);
     dev_free(d_v);
+    g_rap_times[0] = (t_up - t_begin) + (PhaseTimer::now() - t_kern);
+    g_rap_times[1] = t_kern - t_up;
     return rc;
+}
+
+// The values of C = R A P on C's own pattern (see rap_rows_values).  The rows are dealt to the table
+// configurations by their length in C, each configuration is one launch, rows longer than the
+// largest table allowed (SSS_HIP_RAP_CFGS, as in sss_hip_rap) are walked on the host while the
+// kernels run.  The kernels write a device buffer and the host rows a side buffer; C->val receives
+// them only when every row has succeeded (the download is then the call's last step that can fail:
+// a device lost in it leaves C->val partly written).
+extern "C" int sss_hip_rap_values(const SSS_MAT *Rh, const SSS_MAT *Ah, const SSS_MAT *Ph, SSS_MAT *C)
+{
+    g_rap_times[0] = g_rap_times[1] = 0.0;
+    if (!Rh || !Ah || !Ph || !C || !C->row_ptr || !C->col_idx || !C->val) return ERROR_INPUT_PAR;
+    const int nc = Rh->num_rows;
+    if (nc <= 0 || C->num_rows != nc || C->num_cols != nc || Ph->num_cols != nc || Rh->num_cols != Ah->num_rows ||
+        Ah->num_cols != Ph->num_rows || C->num_nnzs < nc)
+        return ERROR_INPUT_PAR;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    if (!row_ptr_ok(*Rh) || !row_ptr_ok(*Ah) || !row_ptr_ok(*Ph) || !row_ptr_ok(*C)) return ERROR_DATA_STRUCTURE;
+    const int nnz = C->num_nnzs;
+    const char *ce = getenv("SSS_HIP_RAP_CFGS");   // tests: fewer device tables, more host rows
+    const int ncfg = (ce && *ce) ? std::max(0, std::min(kCfgs, atoi(ce))) : kCfgs;
+    // the rows of each configuration, back to back in one list; then the host's
+    int cfg_n[kCfgs + 1] = {0, 0, 0, 0, 0}, cfg_at[kCfgs + 2] = {0, 0, 0, 0, 0, 0};
+    auto cfg_of = [&](int ic) {
+        const int len = C->row_ptr[ic + 1] - C->row_ptr[ic];
+        int c = 0;
+        while (c < ncfg && len > kCfgSlots[c]) ++c;
+        return c < ncfg ? c : kCfgs;
+    };
+    for (int ic = 0; ic < nc; ++ic) ++cfg_n[cfg_of(ic)];
+    for (int c = 0; c <= kCfgs; ++c) cfg_at[c + 1] = cfg_at[c] + cfg_n[c];
+    std::vector<int> rows((size_t)nc);
+    {
+        int at[kCfgs + 1];
+        std::copy(cfg_at, cfg_at + kCfgs + 1, at);
+        for (int ic = 0; ic < nc; ++ic) rows[(size_t)at[cfg_of(ic)]++] = ic;
+    }
+    const int ndev = cfg_at[kCfgs], nhost = cfg_n[kCfgs];
+    const int *hrows = rows.data() + ndev;
+    std::vector<long long> hstart((size_t)nhost + 1, 0);   // the host rows' places in their side buffer
+    for (int t = 0; t < nhost; ++t) hstart[(size_t)t + 1] = hstart[t] + (C->row_ptr[hrows[t] + 1] - C->row_ptr[hrows[t]]);
+    HostBuf<double> hvals;
+    hvals.resize((size_t)std::max<long long>(hstart[nhost], 1));
+    std::atomic<int> host_ok{1};
+    auto host_rows = [&] {
+        parallel_chunks(nhost, 64, [&](int a, int e) {
+            std::vector<int> mark((size_t)nc, -1), slot((size_t)nc, 0);
+            for (int t = a; t < e && host_ok; ++t)
+                if (!host_row_values(hrows[t], *Rh, *Ah, *Ph, *C, mark.data(), slot.data(), hvals.data() + hstart[t])) host_ok = 0;
+        });
+    };
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream()
+        {
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } stream;
+    int rc = 0;
+    double t_copy = 0.0, t_kern = 0.0;
+    if (ndev == 0) host_rows();
+    if (ndev > 0) {
+        double t0 = PhaseTimer::now();
+        if (hipStreamCreateWithFlags(&stream.s, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+        hipStream_t st = stream.s;
+        DevMat R, A, P;
+        int *d_crp = nullptr, *d_cci = nullptr, *d_list = nullptr;
+        double *d_v = nullptr;
+        unsigned *d_flag = nullptr, h_flag = 0;
+        const char *what = "hipMalloc(RAP values)";
+        if (R.up(*Rh) || A.up(*Ah) || P.up(*Ph) || dev_upload(d_crp, C->row_ptr, (size_t)nc + 1, what) ||
+            dev_upload(d_cci, C->col_idx, (size_t)nnz, what) || dev_upload(d_list, rows.data(), (size_t)ndev, what))
+            rc = ERROR_MISC;
+        if (!rc) {
+            d_v = dev_alloc<double>((size_t)std::max(nnz, 1));
+            d_flag = dev_alloc<unsigned>(1);
+            if (!d_v || !d_flag || hipMemsetAsync(d_flag, 0, sizeof(unsigned), st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess)
+                rc = ERROR_MISC;
+        }
+        double t1 = PhaseTimer::now();
+        t_copy += t1 - t0;
+        for (int c = 0; c < kCfgs && !rc; ++c) {
+            launch_values_cfg(c, cfg_n[c], d_list + cfg_at[c], *C, R, A, P, d_crp, d_cci, d_v, d_flag, Ah->num_rows,
+                              Ph->num_rows, st);
+            if (hipGetLastError() != hipSuccess) rc = ERROR_MISC;
+        }
+        host_rows();   // (beside the kernels)
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = ERROR_MISC;
+        t0 = PhaseTimer::now();
+        t_kern += t0 - t1;
+        if (!rc && copy_sync(&h_flag, d_flag, sizeof(unsigned), hipMemcpyDeviceToHost, st)) rc = ERROR_MISC;
+        if (!rc && (h_flag || !host_ok)) rc = ERROR_DATA_STRUCTURE;
+        if (!rc && copy_sync(C->val, d_v, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, st)) rc = ERROR_MISC;
+        dev_free(d_crp);
+        dev_free(d_cci);
+        dev_free(d_list);
+        dev_free(d_v);
+        dev_free(d_flag);
+        t_copy += PhaseTimer::now() - t0;
+    }
+    if (!rc && !host_ok) rc = ERROR_DATA_STRUCTURE;
+    if (!rc)
+        parallel_chunks(nhost, 64, [&](int a, int e) {
+            for (int t = a; t < e; ++t)
+                std::memcpy(C->val + C->row_ptr[hrows[t]], hvals.data() + hstart[t], sizeof(double) * (size_t)(hstart[t + 1] - hstart[t]));
+        });
+    g_rap_times[0] = t_copy;
+    g_rap_times[1] = t_kern;
+    return rc;
+}
+
+// (engine-internal, for the refresh's timing line and tools/refresh_measure.py)
+extern "C" void sss_hip_rap_times(double *out)
+{
+    out[0] = g_rap_times[0];
+    out[1] = g_rap_times[1];
 }

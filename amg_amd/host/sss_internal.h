@@ -18,6 +18,12 @@ void sss_dev_release_mirror(const void *cg_key);
 
 /* Returns the HBM mirror for mg, building it on first use (registry keyed by mg->cg). */
 sss_hip_hier *sss_dev_mirror_for(SSS_AMG *mg);
+/* The registered mirror of a hierarchy, or NULL: nothing is built (SSS_amg_refresh). */
+sss_hip_hier *sss_dev_mirror_peek(const void *cg_key);
+
+/* Seconds the calling thread's last sss_hip_rap or sss_hip_rap_values spent in copies (out[0],
+ * allocations included) and in kernels (out[1]). */
+void sss_hip_rap_times(double *out);
 
 /* Fatal HIP/RCCL failure in the product path: print in the reference's style and exit. */
 void sss_fatal(const char *where, const char *what);

@@ -1243,6 +1243,102 @@ SSS_MAT SSS_blas_mat_rap(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P)
     return C;
 }
 
+/* The values of C = R A P on the pattern C already has (the pattern SSS_blas_mat_rap gives for
+ * operators with these patterns): the rule above in one row-parallel pass.  The row's columns go
+ * into the thread's marker arrays with their positions, the diagonal starts at 0.0, every other
+ * slot at -0.0, and every product adds -- x + -0.0 is x for every x, -0.0 included, so a slot's
+ * first product lands as the reference's assignment does.  0, or ERROR_INPUT_PAR (shapes) /
+ * ERROR_DATA_STRUCTURE (an index out of range, a row of C that does not start with its diagonal or
+ * repeats a column, a product whose column the row does not hold) with C->val untouched. */
+int sss_rap_values_host(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P, SSS_MAT *C)
+{
+    if (!R || !A || !P || !C || !C->row_ptr || !C->col_idx || !C->val) return ERROR_INPUT_PAR;
+    const int nc = R->num_rows, nf = A->num_rows, np = P->num_rows;
+    if (nc <= 0 || C->num_rows != nc || C->num_cols != nc || P->num_cols != nc || R->num_cols != nf ||
+        A->num_cols != np || C->num_nnzs < nc || C->row_ptr[0] != 0 || C->row_ptr[nc] != C->num_nnzs)
+        return ERROR_INPUT_PAR;
+    const int *ri = R->row_ptr, *rj = R->col_idx, *ai = A->row_ptr, *aj = A->col_idx;
+    const int *pi = P->row_ptr, *pj = P->col_idx, *ci = C->row_ptr, *cj = C->col_idx;
+    const double *rv = R->val, *av = A->val, *pv = P->val;
+    const int nnz = C->num_nnzs;
+    double *val = (double *)sss_big_malloc(sizeof(double) * (size_t)nnz);
+    int bad = 0;
+    if (!val) return ERROR_ALLOC_MEM;
+#pragma omp parallel
+    {
+        int *seen = (int *)sss_big_malloc(sizeof(int) * (size_t)nc);
+        int *slot = (int *)sss_big_malloc(sizeof(int) * (size_t)nc);
+        for (int i = 0; i < nc; ++i) seen[i] = -1;
+#pragma omp for schedule(dynamic, 256)
+        for (int ic = 0; ic < nc; ++ic) {
+            const int c0 = ci[ic], len = ci[ic + 1] - c0;
+            int ok = len >= 1 && c0 >= 0 && ci[ic + 1] <= nnz && cj[c0] == ic;
+            for (int k = 0; ok && k < len; ++k) {
+                const int c = cj[c0 + k];
+                if (c < 0 || c >= nc || seen[c] == ic) {
+                    ok = 0;
+                    break;
+                }
+                seen[c] = ic;
+                slot[c] = c0 + k;
+                val[c0 + k] = k == 0 ? 0.0 : -0.0;
+            }
+            for (int q1 = ri[ic]; ok && q1 < ri[ic + 1]; ++q1) {
+                const double r = rv[q1];
+                const int i1 = rj[q1];
+                if (i1 < 0 || i1 >= nf) {
+                    ok = 0;
+                    break;
+                }
+                for (int q2 = ai[i1]; ok && q2 < ai[i1 + 1]; ++q2) {
+                    const double ra = r * av[q2];
+                    const int i2 = aj[q2];
+                    if (i2 < 0 || i2 >= np) {
+                        ok = 0;
+                        break;
+                    }
+                    for (int q3 = pi[i2]; q3 < pi[i2 + 1]; ++q3) {
+                        const int i3 = pj[q3];
+                        if (i3 < 0 || i3 >= nc || seen[i3] != ic) {
+                            ok = 0;
+                            break;
+                        }
+                        val[slot[i3]] += ra * pv[q3];
+                    }
+                }
+            }
+            if (!ok) {
+#pragma omp atomic write
+                bad = 1;
+            }
+        }
+        free(seen);
+        free(slot);
+    }
+    if (!bad) {
+#pragma omp parallel for schedule(static)
+        for (int k = 0; k < nnz; ++k) C->val[k] = val[k];
+    }
+    free(val);
+    return bad ? ERROR_DATA_STRUCTURE : 0;
+}
+
+/* The setup's rule for a level's Galerkin product on the GPU: a device is present and
+ * SSS_SETUP_GPU_RAP is not 0; A_l has at least SSS_SETUP_GPU_RAP_MIN nonzeros (default 10^6) and
+ * at most SSS_SETUP_GPU_RAP_MAXROW of them per row on average (default 48). */
+static int gpu_rap_enabled(void)
+{
+    const char *gr = getenv("SSS_SETUP_GPU_RAP");
+    return !(gr && gr[0] == '0') && sss_hip_device_count() > 0;
+}
+static int gpu_rap_level(const SSS_MAT *A)
+{
+    const char *grm = getenv("SSS_SETUP_GPU_RAP_MIN"), *grx = getenv("SSS_SETUP_GPU_RAP_MAXROW");
+    const int gpu_rap_min = (grm && *grm) ? atoi(grm) : 1000000;
+    const int gpu_rap_maxrow = (grx && *grx) ? atoi(grx) : 48;
+    return A->num_nnzs >= gpu_rap_min && (double)A->num_nnzs <= (double)gpu_rap_maxrow * A->num_rows;
+}
+
 /* ======================================================================================
  * Level loop (Setup/SSS_SETUP.cu:5-178)
  * ====================================================================================== */
@@ -1281,12 +1377,7 @@ void sss_amg_setup_hooked(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, sss_setup
     const double t0 = SSS_get_time();
     SSS_IVEC vertices;
     int lvl = 0;
-    /* the Galerkin products of the large levels on the GPU when one is present (same result) */
-    const char *gr = getenv("SSS_SETUP_GPU_RAP"), *grm = getenv("SSS_SETUP_GPU_RAP_MIN");
-    const int use_gpu_rap = !(gr && gr[0] == '0') && sss_hip_device_count() > 0;
-    const int gpu_rap_min = (grm && *grm) ? atoi(grm) : 1000000;
-    const char *grx = getenv("SSS_SETUP_GPU_RAP_MAXROW");   /* average A row length up to which */
-    const int gpu_rap_maxrow = (grx && *grx) ? atoi(grx) : 48;
+    const int use_gpu_rap = gpu_rap_enabled();
 
     *mg = SSS_amg_data_create(pars);
     vertices = SSS_ivec_create(n0);
@@ -1341,8 +1432,7 @@ void sss_amg_setup_hooked(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, sss_setup
         /* the device walks each coarse row's (R entry, A entry) steps in order, so it wins on the
          * wide levels of short rows (7-pt 400^3 levels 0-2: 3.1 -> 1.1, 2.0 -> 0.75, 0.59 -> 0.37 s)
          * and loses on the narrow levels of long rows (level 3 and below: 0.75 -> 1.2 s) */
-        const int gpu_here = use_gpu_rap && L->A.num_nnzs >= gpu_rap_min &&
-                             (double)L->A.num_nnzs <= (double)gpu_rap_maxrow * L->A.num_rows;
+        const int gpu_here = use_gpu_rap && gpu_rap_level(&L->A);
         if (!(gpu_here && sss_hip_rap(&L->R, &L->A, &L->P, &mg->cg[lvl + 1].A) == 0))
             mg->cg[lvl + 1].A = SSS_blas_mat_rap(&L->R, &L->A, &L->P);
         sss_trace_pop();
@@ -1376,4 +1466,45 @@ void sss_amg_setup_hooked(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, sss_setup
     SSS_amg_complexity_print(mg);
     printf("AMG setup time: %g s\n", SSS_get_time() - t0);
     if (hook) hook(ctx, mg, mg->num_levels - 1, 1);
+}
+
+/* ======================================================================================
+ * Refresh of a set-up hierarchy for new operator values on the same pattern: C/F marks, P and R
+ * stay, the Galerkin chain is recomputed as values-only products.
+ * ====================================================================================== */
+int SSS_amg_refresh(SSS_AMG *mg, const SSS_MAT *A)
+{
+    if (!mg || !A || !mg->cg || mg->num_levels < 1) return ERROR_INPUT_PAR;
+    SSS_MAT *A0 = &mg->cg[0].A;
+    if (A->num_rows != A0->num_rows || A->num_cols != A0->num_cols || A->num_nnzs != A0->num_nnzs || !A->row_ptr ||
+        !A->col_idx || !A->val ||
+        memcmp(A->row_ptr, A0->row_ptr, sizeof(int) * ((size_t)A0->num_rows + 1)) != 0 ||
+        memcmp(A->col_idx, A0->col_idx, sizeof(int) * (size_t)A0->num_nnzs) != 0)
+        return ERROR_INPUT_PAR;
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const int use_gpu_rap = gpu_rap_enabled();
+    if (A->val != A0->val) memcpy(A0->val, A->val, sizeof(double) * (size_t)A0->num_nnzs);
+    for (int l = 0; l + 1 < mg->num_levels; ++l) {
+        SSS_AMG_COMP *L = &mg->cg[l];
+        SSS_MAT *C = &mg->cg[l + 1].A;
+        const double t0 = SSS_get_time();
+        int on_device = use_gpu_rap && gpu_rap_level(&L->A) && sss_hip_rap_values(&L->R, &L->A, &L->P, C) == 0;
+        if (!on_device) {
+            const int rc = sss_rap_values_host(&L->R, &L->A, &L->P, C);
+            if (rc) return rc;
+        }
+        if (timing) {
+            double t[2] = {0.0, 0.0};
+            if (on_device) sss_hip_rap_times(t);
+            if (on_device)
+                fprintf(stderr, "[refresh] level %d: device %.3f s (copies %.3f s, kernels %.3f s)\n", l,
+                        SSS_get_time() - t0, t[0], t[1]);
+            else
+                fprintf(stderr, "[refresh] level %d: host %.3f s\n", l, SSS_get_time() - t0);
+        }
+    }
+    /* the drop-in path's mirror follows; one that cannot is dropped, and the next solve builds it again */
+    sss_hip_hier *h = sss_dev_mirror_peek(mg->cg);
+    if (h && sss_hip_hier_refresh(h, mg) != 0) sss_dev_release_mirror(mg->cg);
+    return 0;
 }

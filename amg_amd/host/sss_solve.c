@@ -62,6 +62,13 @@ static void sss_dev_adopt_mirror(SSS_AMG *mg, sss_hip_hier *h)
     sss_hip_hier_destroy(h);   /* no slot: the first solve builds it again */
 }
 
+sss_hip_hier *sss_dev_mirror_peek(const void *cg_key)
+{
+    for (int s = 0; s < MIRROR_SLOTS; ++s)
+        if (g_mirrors[s].key == cg_key && g_mirrors[s].h) return g_mirrors[s].h;
+    return NULL;
+}
+
 void sss_dev_release_mirror(const void *cg_key)
 {
     for (int s = 0; s < MIRROR_SLOTS; ++s) {

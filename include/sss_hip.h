@@ -89,6 +89,17 @@ typedef struct sss_hip_hier sss_hip_hier;
  * smoother schedules.  mg->cg[0].x/.b may be unset. Returns NULL on failure. */
 sss_hip_hier *sss_hip_hier_create(const SSS_AMG *mg, const sss_hip_opts *o);
 void sss_hip_hier_destroy(sss_hip_hier *h);
+/* mg is the hierarchy h mirrors, after SSS_amg_refresh: the value-dependent half of the mirror is
+ * built again level by level -- A_l in its formats, the smoother plan, the coarse solver, the
+ * single-workgroup tail, the captured graphs; a level's old A objects are released before its new
+ * ones are built.  The stream, the relabelings, every level's vectors (the level-0 b and x keep
+ * their contents), the Krylov workspaces and the P_l / R_l device objects are kept; a level whose
+ * plan flag behind P's storage changed with the values rebuilds its P and R as well.  After a
+ * return of 0 every engine call on h gives bitwise what it gives on a mirror newly created from mg
+ * with h's options, and sss_hip_level_info_get agrees field for field.  Works on mirrors from
+ * sss_hip_hier_create and sss_hip_setup_create.  On failure: an error code, and h is good only
+ * for sss_hip_hier_destroy. */
+int sss_hip_hier_refresh(sss_hip_hier *h, const SSS_AMG *mg);
 
 /* SSS_amg_setup (Setup/SSS_SETUP.cu:36-178 semantics, same printed output, same mg) with the
  * mirror built while the setup runs: every level is relabeled and uploaded on a worker thread as
@@ -106,6 +117,22 @@ sss_hip_hier *sss_hip_setup_create(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, 
  * nonzeros in A (default 10^6) and at most SSS_SETUP_GPU_RAP_MAXROW of them per row on average
  * (default 48); SSS_SETUP_GPU_RAP=0 keeps every product on the host. */
 int sss_hip_rap(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P, SSS_MAT *C);
+/* The values of that product on a pattern already known (SSS_amg_refresh).
+ * C has row_ptr / col_idx of a product of operators with these patterns (SSS_blas_mat_rap or sss_hip_rap);
+ * fills C->val with the values that product would give, bit for bit.  0, or an error code with C->val untouched
+ * (ERROR_INPUT_PAR: shapes that do not fit; ERROR_DATA_STRUCTURE: an index out of range, a row of C that
+ * does not start with its diagonal or repeats a column, a product whose column is absent from the
+ * row of C; the device call also: no device, no memory, a failed copy -- the kernels write a device
+ * buffer that is downloaded into C->val only after every row has succeeded, so only a device lost
+ * during that last download can leave C->val partly written).
+ * The rule "the first product of a column opens a slot, every later one adds" makes the pattern a
+ * function of the three patterns alone, so here a row's column -> slot table is filled from the row
+ * of C, the diagonal starts at 0.0 and every other slot at -0.0, and every product adds in the
+ * reference's order (x + -0.0 is x for every x, -0.0 included).  One kernel pass on the device: no
+ * count pass, no prefix sum, no retry; the table size is chosen from the row's length, rows longer than
+ * the largest table (4,096; SSS_HIP_RAP_CFGS lowers it as for sss_hip_rap) are walked on the host. */
+int sss_hip_rap_values(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P, SSS_MAT *C);
+int sss_rap_values_host(const SSS_MAT *R, const SSS_MAT *A, const SSS_MAT *P, SSS_MAT *C);   /* OpenMP, row-parallel */
 
 /* The PMIS C/F split (cs_type SSS_COARSE_PMIS; the rule: DESIGN.md "PMIS coarsening") of a compacted
  * strength matrix S (row_ptr, col_idx; square) on the GPU: S is uploaded, the rounds run as ordinary
@@ -166,6 +193,17 @@ int sss_hip_residual_norm(sss_hip_hier *h, double *absres);
  * SSS_amg_data_destroy).  0 or ERROR_OPEN_FILE / ERROR_WRONG_FILE. */
 int SSS_amg_save(const SSS_AMG *mg, const char *path);
 int SSS_amg_load(SSS_AMG *mg, const char *path);
+/* New operator values on the pattern of a set-up (or loaded) hierarchy (engine extension, DESIGN.md
+ * 6.6): A must have the dimensions, row_ptr and col_idx of mg->cg[0].A, else ERROR_INPUT_PAR with mg
+ * untouched.  The values are copied into level 0 and A_{l+1} = R_l A_l P_l is recomputed down the
+ * levels as values-only products (sss_hip_rap_values under the rule the setup uses for sss_hip_rap
+ * -- SSS_SETUP_GPU_RAP, _MIN, _MAXROW, a device being present -- else, and on any device error,
+ * sss_rap_values_host).  P, R, cfmark and the level vectors are untouched; a one-level hierarchy
+ * is just the copy.  Nothing on stdout; under SSS_SETUP_TIMING one stderr line per level.  A mirror
+ * the drop-in solve path holds for mg is refreshed too (sss_hip_hier_refresh), or released when
+ * that fails, so that the next solve builds it again.
+ * Frozen P carries the old near-null space: see the limit in DESIGN.md 6.6. */
+int SSS_amg_refresh(SSS_AMG *mg, const SSS_MAT *A);
 
 /* AMG-preconditioned flexible CG on level 0 (an engine extension -- the
  * reference's Krylov solvers serve only the coarsest level): right-hand side = the level-0 b
