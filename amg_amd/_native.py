@@ -116,7 +116,7 @@ ABI_SYMBOLS = [
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
     "SSS_amg_save", "SSS_amg_load",
-    "sss_hip_coarse_solve", "sss_hip_smooth", "sss_hip_sync", "sss_hip_level_info_get", "sss_hip_num_levels", "sss_hip_tail_from",
+    "sss_hip_coarse_solve", "sss_hip_coarse_last", "sss_hip_smooth", "sss_hip_sync", "sss_hip_level_info_get", "sss_hip_num_levels", "sss_hip_tail_from",
     "sss_hip_cycle_launches", "sss_hip_cycle_bytes",
     "sss_hip_merged_narrow", "sss_hip_merged_key_stats", "sss_hip_merged_keys_get",
     "sss_hip_spmv_plan_create", "sss_hip_spmv_plan_destroy", "sss_hip_spmv", "sss_hip_host_spmv", "sss_hip_host_spmv_order",
@@ -214,6 +214,7 @@ def _declare(lib):
         "SSS_amg_save": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "SSS_amg_load": (C.c_int, [P(SSS_AMG), C.c_char_p]),
         "sss_hip_coarse_solve": (C.c_int, [C.c_void_p]),
+        "sss_hip_coarse_last": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
         "sss_hip_smooth": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
         "sss_hip_sync": (C.c_int, [C.c_void_p]),
         "sss_hip_level_info_get": (C.c_int, [C.c_void_p, C.c_int, P(SSS_HIP_LEVEL_INFO)]),
@@ -490,6 +491,21 @@ class Hierarchy:
             pass
 
 
+#: the fields of sss_hip_coarse_last, in order (sss_hip.h)
+COARSE_LAST_FIELDS = ("form", "cg_status", "cg_iter", "cg_iter_best", "cg_stag", "cg_more_step",
+                      "gm_ran", "gm_status", "gm_iter", "gm_cycles")
+
+
+def coarse_last(h=None) -> dict:
+    """The route of the last Krylov coarse solve: on the hierarchy handle h, or (h None) of the last
+    sss_hip_host_coarse_solve on this thread."""
+    out = (C.c_int * len(COARSE_LAST_FIELDS))()
+    rc = lib().sss_hip_coarse_last(h, out, len(COARSE_LAST_FIELDS))
+    if rc != len(COARSE_LAST_FIELDS):
+        raise RuntimeError(f"sss_hip_coarse_last: no completed Krylov coarse solve (code {rc})")
+    return dict(zip(COARSE_LAST_FIELDS, out))
+
+
 class DeviceHierarchy:
     """HBM mirror of a Hierarchy (sss_hip_hier_create)."""
 
@@ -588,6 +604,10 @@ class DeviceHierarchy:
 
     def coarse_solve(self):
         self._check(lib().sss_hip_coarse_solve(self.h), "coarse_solve")
+
+    def coarse_last(self) -> dict:
+        """The route of the last Krylov coarse solve on this hierarchy (sss_hip_coarse_last)."""
+        return coarse_last(self.h)
 
     def sync(self):
         self._check(lib().sss_hip_sync(self.h), "sync")

@@ -60,6 +60,8 @@ struct CoarseKrylov {
     CgState *h_st = nullptr;   // pinned
     double *gp = nullptr, *gw = nullptr, *gx_best = nullptr, *hcol = nullptr, *rs_dev = nullptr, *scal = nullptr;
     double *h_buf = nullptr;   // pinned, >= 64 doubles
+    int last[SSS_HIP_COARSE_LAST_N] = {};   // the route of the last solve (sss_hip_coarse_last)
+    bool last_valid = false;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1272,6 +1274,12 @@ static int run_cg(CoarseKrylov *k, const DevCSR &A, const double *b, double *u, 
         return ERROR_MISC;
     }
     *status = k->h_st->status;
+    k->last[SSS_HIP_CL_FORM] = persist ? 2 : reg_step ? 1 : 0;
+    k->last[SSS_HIP_CL_CG_STATUS] = k->h_st->status;
+    k->last[SSS_HIP_CL_CG_ITER] = k->h_st->iter;
+    k->last[SSS_HIP_CL_CG_ITER_BEST] = k->h_st->iter_best;
+    k->last[SSS_HIP_CL_CG_STAG] = k->h_st->stag;
+    k->last[SSS_HIP_CL_CG_MORE_STEP] = k->h_st->more_step;
     return 0;
 }
 
@@ -1282,7 +1290,7 @@ static int run_gmres(CoarseKrylov *k, const DevCSR &A, const double *b, double *
     const double maxdiff = tol * 1e-4;
     double hh[max_RESTART + 1][max_RESTART] = {}, c[max_RESTART] = {}, sn[max_RESTART] = {}, rs[max_RESTART + 1] = {};
     double r_norm, normr0, absres = BIGFLOAT, relres, absres_best = BIGFLOAT, t, gamma;
-    int iter = 0, iter_best = 0, i = 0, rc;
+    int iter = 0, iter_best = 0, i = 0, rc, cycles = 0;
     double *P = k->gp;
     auto pv = [&](int q) { return P + (size_t)q * n; };
     auto upload_rs = [&]() -> int {
@@ -1297,11 +1305,13 @@ static int run_gmres(CoarseKrylov *k, const DevCSR &A, const double *b, double *
     if ((rc = host_resid_norm(k, A, x, b, pv(0), &r_norm, s))) return rc;
     normr0 = fmax(SMALLFLOAT, r_norm);
     relres = r_norm / normr0;
+    k->last[SSS_HIP_CL_GM_RAN] = 1;
     if (relres < tol) {
         *status = 0;
         return 0;
     }
     while (iter < maxit) {
+        ++cycles;
         rs[0] = r_norm;
         t = 1.0 / r_norm;
         hipLaunchKernelGGL(k_scal, dim3(nbe), dim3(kBlock), 0, s, n, t, pv(0));
@@ -1372,7 +1382,18 @@ static int run_gmres(CoarseKrylov *k, const DevCSR &A, const double *b, double *
     SSS_HIP(hipGetLastError());
     SSS_HIP(hipStreamSynchronize(s));
     *status = iter >= maxit ? ERROR_SOLVER_matrix : iter;
+    k->last[SSS_HIP_CL_GM_STATUS] = *status;
+    k->last[SSS_HIP_CL_GM_ITER] = iter;
+    k->last[SSS_HIP_CL_GM_CYCLES] = cycles;
     return 0;
+}
+
+int coarse_krylov_last(const CoarseKrylov *k, int *out, int n)
+{
+    if (!k || !k->last_valid || !out) return ERROR_INPUT_PAR;
+    const int m = std::min(std::max(n, 0), (int)SSS_HIP_COARSE_LAST_N);
+    for (int i = 0; i < m; ++i) out[i] = k->last[i];
+    return m;
 }
 
 int coarse_krylov_solve(CoarseKrylov *k, const DevCSR &A, const double *b, double *x, double ctol, hipStream_t s)
@@ -1381,8 +1402,11 @@ int coarse_krylov_solve(CoarseKrylov *k, const DevCSR &A, const double *b, doubl
     const int nn = (int)(long long)((long long)n * n);   // n*n in int, as the reference
     const int maxit = std::max(250, std::min(nn, 1000));
     int status = 0, rc;
+    k->last_valid = false;
+    std::memset(k->last, 0, sizeof(k->last));
     if ((rc = run_cg(k, A, b, x, ctol, maxit, s, &status))) return rc;
     if (status < 0 && (rc = run_gmres(k, A, b, x, ctol, maxit, s, &status))) return rc;
+    k->last_valid = true;
     if (status < 0 && getenv("SSS_HIP_WARN_COARSE")) printf("### WARNING: Coarse level solver failed to converge!\n");
     return 0;
 }

@@ -760,5 +760,7 @@ CoarseKrylov *coarse_krylov_create(const DevCSR &A, int row_cap, hipStream_t str
 void coarse_krylov_destroy(CoarseKrylov *k);
 int coarse_krylov_solve(CoarseKrylov *k, const DevCSR &A, const double *b, double *x, double ctol,
                         hipStream_t stream);
+// the route of the last coarse_krylov_solve on k (sss_hip_coarse_last): fields copied, or an error code
+int coarse_krylov_last(const CoarseKrylov *k, int *out, int n);
 
 }  // namespace sss

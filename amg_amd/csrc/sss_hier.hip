@@ -1058,6 +1058,20 @@ extern "C" int sss_hip_coarse_solve(sss_hip_hier *h)
     return coarse_krylov_solve(h->krylov, C.A, C.b, C.x, tol, h->stream);
 }
 
+// the last sss_hip_host_coarse_solve on this thread (the cached CoarseKrylov may be gone by the time
+// the caller asks)
+static thread_local int t_host_coarse_last[SSS_HIP_COARSE_LAST_N];
+static thread_local int t_host_coarse_last_n = ERROR_INPUT_PAR;
+
+extern "C" int sss_hip_coarse_last(sss_hip_hier *h, int *out, int n)
+{
+    if (h) return coarse_krylov_last(h->coarse_mode == SSS_HIP_COARSE_DIRECT ? nullptr : h->krylov, out, n);
+    if (t_host_coarse_last_n < 0 || !out) return ERROR_INPUT_PAR;
+    const int m = std::min(std::max(n, 0), t_host_coarse_last_n);
+    for (int i = 0; i < m; ++i) out[i] = t_host_coarse_last[i];
+    return m;
+}
+
 extern "C" int sss_hip_smooth(sss_hip_hier *h, int level, int post)
 {
     auto &L = h->L[level];
@@ -1932,6 +1946,7 @@ extern "C" int sss_hip_host_smooth(const SSS_SMTR *s, int post)
 extern "C" int sss_hip_host_coarse_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, double ctol, int coarse_mode,
                                          int row_cap)
 {
+    t_host_coarse_last_n = ERROR_INPUT_PAR;
     if (sss_hip_device_count() <= 0) return ERROR_MISC;
     const int n = A->num_rows;
     const bool direct = coarse_mode == SSS_HIP_COARSE_DIRECT && n <= 20000;
@@ -1965,6 +1980,7 @@ extern "C" int sss_hip_host_coarse_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, dou
         } else {
             rc = coarse_krylov_solve(M->k, M->d, db, dx, ctol, nullptr);
         }
+        if (!direct) t_host_coarse_last_n = coarse_krylov_last(M->k, t_host_coarse_last, SSS_HIP_COARSE_LAST_N);
     }
     if (!rc && hipMemcpy(x->d, dx, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
     dev_free(dx);

@@ -232,6 +232,26 @@ int sss_hip_fgmres(sss_hip_hier *h, double tol, int restart, int maxit, int *ite
                    int hist_cap);
 /* The coarsest-level solve alone (on the level vectors of the coarsest level). */
 int sss_hip_coarse_solve(sss_hip_hier *h);
+/* The route the last Krylov coarse solve took, for tests: with a hierarchy, the last
+ * sss_hip_coarse_solve on h (a cycle's included); with h == NULL, the last
+ * sss_hip_host_coarse_solve on the calling thread.  Copies min(n, SSS_HIP_COARSE_LAST_N) fields and
+ * returns their number; ERROR_INPUT_PAR where no Krylov coarse solve has completed (none yet, the
+ * explicit inverse, or a solve that returned an error).  Every field is a value the host already
+ * holds when the solve returns: reading it costs the cycle nothing. */
+enum {
+    SSS_HIP_CL_FORM = 0,      /* the CG form that ran: 0 LDS-chunked step, 1 register step, 2 one launch */
+    SSS_HIP_CL_CG_STATUS,     /* SSS_solver_cg's return value */
+    SSS_HIP_CL_CG_ITER,       /* iter as the loop left it (maxit + 1 after a full run, an error code) */
+    SSS_HIP_CL_CG_ITER_BEST,
+    SSS_HIP_CL_CG_STAG,
+    SSS_HIP_CL_CG_MORE_STEP,
+    SSS_HIP_CL_GM_RAN,        /* 1: CG's status was negative and SSS_solver_gmres ran */
+    SSS_HIP_CL_GM_STATUS,
+    SSS_HIP_CL_GM_ITER,
+    SSS_HIP_CL_GM_CYCLES,     /* Krylov cycles (passes of the restart loop) */
+    SSS_HIP_COARSE_LAST_N
+};
+int sss_hip_coarse_last(sss_hip_hier *h, int *out, int n);
 /* Pre (post = 0) or post (post = 1) smoothing of one level. */
 int sss_hip_smooth(sss_hip_hier *h, int level, int post);
 int sss_hip_sync(sss_hip_hier *h);

@@ -56,6 +56,7 @@ def load():
             "ora_cg": (C.c_int, [P(SSS_KRYLOV), C.c_int]),
             "ora_gmres": (C.c_int, [P(SSS_KRYLOV), C.c_int]),
             "ora_coarest_solve": (None, [P(SSS_MAT), P(SSS_VEC), P(SSS_VEC), C.c_double, P(ORA_OPTS)]),
+            "ora_krylov_events": (None, [ip, C.c_int]),
             "ora_cycle": (None, [P(SSS_AMG), P(ORA_OPTS)]),
             "ora_solve": (SSS_RTN, [P(SSS_AMG), P(SSS_VEC), P(SSS_VEC), P(ORA_OPTS), dp, dp, C.c_int]),
             "ora_coarse_seconds": (C.c_double, []),
@@ -67,6 +68,24 @@ def load():
             fn.restype, fn.argtypes = res, args
         _ora = lib
     return _ora
+
+
+#: the slots of ora_krylov_events, in order (sss_oracle.h): the events of ora_cg and ora_gmres ...
+KRYLOV_EVENTS = ("cg_breakdown", "cg_solstag", "cg_check2", "cg_check2_conv", "cg_stag_exit", "cg_check3",
+                 "cg_check3_conv", "cg_tolsmall_exit", "cg_stag_inc", "cg_more_step_inc", "cg_best_copied",
+                 "cg_immediate", "cg_maxit",
+                 "gm_immediate", "gm_cycles", "gm_early_break", "gm_recheck_failed", "gm_recombine",
+                 "gm_best_copied", "gm_maxit")
+#: ... then both statuses, whether GMRES ran, and the counters the loops ended with
+KRYLOV_FIELDS = KRYLOV_EVENTS + ("cg_status", "cg_iter", "cg_iter_best", "cg_stag", "cg_more_step",
+                                 "gm_ran", "gm_status", "gm_iter")
+
+
+def krylov_events() -> dict:
+    """The route of the last ora_cg / ora_gmres / ora_coarest_solve call on this thread."""
+    out = (C.c_int * len(KRYLOV_FIELDS))()
+    load().ora_krylov_events(out, len(KRYLOV_FIELDS))
+    return dict(zip(KRYLOV_FIELDS, out))
 
 
 def opts(**kw) -> ORA_OPTS:

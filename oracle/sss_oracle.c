@@ -385,6 +385,16 @@ static void residual_into(const SSS_MAT *A, const double *b, const double *u, do
     ora_mv_amxpy(-1.0, A, u, r, cap);
 }
 
+/* the route of the last coarse Krylov call on this thread (ora_krylov_events): counters only */
+static __thread int g_kev[ORA_KR_COUNT];
+static __thread int g_in_coarse = 0;   /* ora_gmres as ora_coarest_solve's fallback keeps the CG slots */
+#define KEV(e) (++g_kev[ORA_EV_##e])
+
+void ora_krylov_events(int *out, int n)
+{
+    for (int i = 0; i < n && i < ORA_KR_COUNT; ++i) out[i] = g_kev[i];
+}
+
 int ora_cg(SSS_KRYLOV *ks, int cap)
 {
     SSS_MAT *A = ks->A;
@@ -398,12 +408,16 @@ int ora_cg(SSS_KRYLOV *ks, int cap)
     double absres0, absres = BIGFLOAT, relres, normr0, absres_best = BIGFLOAT;
     double alpha, temp1, temp2;
 
+    memset(g_kev, 0, sizeof(g_kev));
     residual_into(A, b, u, r, m, cap);
     copy(m, r, z);
     absres0 = nrm2(m, r);
     normr0 = SSS_max(SMALLFLOAT, absres0);
     relres = absres0 / normr0;
-    if (relres < tol) goto done;
+    if (relres < tol) {
+        KEV(CG_IMMEDIATE);
+        goto done;
+    }
     copy(m, z, p);
     temp1 = dot(m, z, r); /* frozen for the whole solve: Solve/SSS_cycle.cu:373-374 as compiled */
 
@@ -411,7 +425,10 @@ int ora_cg(SSS_KRYLOV *ks, int cap)
         ora_mv_acc(A, p, t, cap);          /* t += A*p: t is never cleared */
         temp2 = dot(m, t, p);
         if (SSS_ABS(temp2) > SMALLFLOAT2) alpha = temp1 / temp2;
-        else goto restore;
+        else {
+            KEV(CG_BREAKDOWN);
+            goto restore;
+        }
         axpy(m, alpha, p, u);
         axpy(m, -alpha, t, r);
         absres = nrm2(m, r);
@@ -422,6 +439,7 @@ int ora_cg(SSS_KRYLOV *ks, int cap)
             copy(m, u, u_best);
         }
         if (nrminf(m, u) <= SMALLFLOAT) {
+            KEV(CG_SOLSTAG);
             iter = ERROR_SOLVER_SOLSTAG;
             break;
         }
@@ -429,29 +447,41 @@ int ora_cg(SSS_KRYLOV *ks, int cap)
             const double normu = nrm2(m, u);
             const double reldiff = SSS_ABS(alpha) * nrm2(m, p) / normu;
             if ((stag <= max_STAG) & (reldiff < maxdiff)) {
+                KEV(CG_CHECK2);
                 residual_into(A, b, u, r, m, cap);
                 absres = nrm2(m, r);
                 relres = absres / normr0;
-                if (relres < tol) break;
+                if (relres < tol) {
+                    KEV(CG_CHECK2_CONV);
+                    break;
+                }
                 if (stag >= max_STAG) {
+                    KEV(CG_STAG_EXIT);
                     iter = ERROR_SOLVER_STAG;
                     break;
                 }
                 memset(p, 0, sizeof(double) * (size_t)m);
                 ++stag;
+                KEV(CG_STAG_INC);
             }
         }
         if (relres < tol) {
+            KEV(CG_CHECK3);
             residual_into(A, b, u, r, m, cap);
             absres = nrm2(m, r);
             relres = absres / normr0;
-            if (relres < tol) break;
+            if (relres < tol) {
+                KEV(CG_CHECK3_CONV);
+                break;
+            }
             if (more_step >= max_RESTART) {
+                KEV(CG_TOLSMALL_EXIT);
                 iter = ERROR_SOLVER_TOLSMALL;
                 break;
             }
             memset(p, 0, sizeof(double) * (size_t)m);
             ++more_step;
+            KEV(CG_MORE_STEP_INC);
         }
         absres0 = absres;
         copy(m, r, z);
@@ -463,11 +493,20 @@ restore:
     if (iter != iter_best) {
         residual_into(A, b, u_best, r, m, cap);
         absres_best = nrm2(m, r);
-        if (absres > absres_best + maxdiff) copy(m, u_best, u);
+        if (absres > absres_best + maxdiff) {
+            KEV(CG_BEST_COPIED);
+            copy(m, u_best, u);
+        }
     }
 done:
     free(work);
     (void)absres0;
+    if (iter > maxit) KEV(CG_MAXIT);
+    g_kev[ORA_KR_CG_STATUS] = iter > maxit ? ERROR_SOLVER_matrix : iter;
+    g_kev[ORA_KR_CG_ITER] = iter;
+    g_kev[ORA_KR_CG_ITER_BEST] = iter_best;
+    g_kev[ORA_KR_CG_STAG] = stag;
+    g_kev[ORA_KR_CG_MORE_STEP] = more_step;
     return iter > maxit ? ERROR_SOLVER_matrix : iter;
 }
 
@@ -488,13 +527,18 @@ int ora_gmres(SSS_KRYLOV *ks, int cap)
     for (int q = 0; q < restart1; ++q) p[q] = s + restart + (size_t)q * n;
     for (int q = 0; q < restart1; ++q) hh[q] = p[restart] + n + (size_t)q * restart;
 
+    if (!g_in_coarse) memset(g_kev, 0, sizeof(g_kev));
     residual_into(A, b, x, p[0], n, cap);
     r_norm = nrm2(n, p[0]);
     normr0 = SSS_max(SMALLFLOAT, r_norm);
     relres = r_norm / normr0;
-    if (relres < tol) goto done;
+    if (relres < tol) {
+        KEV(GM_IMMEDIATE);
+        goto done;
+    }
 
     while (iter < maxit) {
+        KEV(GM_CYCLES);
         rs[0] = r_norm;
         scal(n, 1.0 / r_norm, p[0]);
         i = 0;
@@ -526,7 +570,10 @@ int ora_gmres(SSS_KRYLOV *ks, int cap)
             hh[i - 1][i - 1] = s[i - 1] * hh[i][i - 1] + c[i - 1] * hh[i - 1][i - 1];
             absres = r_norm = fabs(rs[i]);
             relres = absres / normr0;
-            if (relres <= tol) break;
+            if (relres <= tol) {
+                KEV(GM_EARLY_BREAK);
+                break;
+            }
         }
         /* back substitution and update */
         rs[i - 1] = rs[i - 1] / hh[i - 1][i - 1];
@@ -552,6 +599,7 @@ int ora_gmres(SSS_KRYLOV *ks, int cap)
             absres = r_norm;
             relres = absres / normr0;
             if (relres <= tol) break;
+            KEV(GM_RECHECK_FAILED);
             copy(n, r, p[0]);
             i = 0;
         }
@@ -562,6 +610,7 @@ int ora_gmres(SSS_KRYLOV *ks, int cap)
         if (i) axpy(n, rs[i] - 1.0, p[i], p[i]);
         for (int j = i - 1; j > 0; j--) axpy(n, rs[j], p[j], p[i]);
         if (i) {
+            KEV(GM_RECOMBINE);
             axpy(n, rs[0] - 1.0, p[0], p[0]);
             axpy(n, 1.0, p[i], p[0]);
         }
@@ -570,12 +619,19 @@ int ora_gmres(SSS_KRYLOV *ks, int cap)
     if (iter != iter_best) {
         residual_into(A, b, x_best, r, n, cap);
         absres_best = nrm2(n, r);
-        if (absres > absres_best + maxdiff) copy(n, x_best, x);
+        if (absres > absres_best + maxdiff) {
+            KEV(GM_BEST_COPIED);
+            copy(n, x_best, x);
+        }
     }
 done:
     free(work);
     free(p);
     free(hh);
+    if (iter >= maxit) KEV(GM_MAXIT);
+    g_kev[ORA_KR_GM_RAN] = 1;
+    g_kev[ORA_KR_GM_STATUS] = iter >= maxit ? ERROR_SOLVER_matrix : iter;
+    g_kev[ORA_KR_GM_ITER] = iter;
     return iter >= maxit ? ERROR_SOLVER_matrix : iter;
 }
 
@@ -651,6 +707,7 @@ void ora_coarest_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, double ctol, const or
     int status;
 
     if (o && o->coarse_mode == 1) {
+        memset(g_kev, 0, sizeof(g_kev));
         lu_solve(A, b->d, x->d);
         g_coarse_seconds += now_s() - t0;
         return;
@@ -665,7 +722,9 @@ void ora_coarest_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, double ctol, const or
     status = ora_cg(&ks, o ? o->row_cap : 0);
     if (status < 0) {
         ks.restart = max_RESTART;
+        g_in_coarse = 1;
         status = ora_gmres(&ks, o ? o->row_cap : 0);
+        g_in_coarse = 0;
     }
     if (status < 0 && (!o || o->verbose)) printf("### WARNING: Coarse level solver failed to converge!\n");
     g_coarse_seconds += now_s() - t0;

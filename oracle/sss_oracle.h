@@ -56,6 +56,45 @@ int ora_gmres(SSS_KRYLOV *ks, int cap);
 void ora_coarest_solve(SSS_MAT *A, SSS_VEC *b, SSS_VEC *x, double ctol, const ora_opts *o);
 void ora_cycle(SSS_AMG *mg, const ora_opts *o);
 
+/* The route the last ora_cg / ora_gmres / ora_coarest_solve call on this thread took: how often each
+ * branch of the two state machines ran, then the statuses and the final counters.  Counting only:
+ * no arithmetic depends on it.  ora_cg clears every slot; ora_gmres called on its own clears the CG
+ * slots as well; the dense-LU coarse mode leaves every slot at zero. */
+enum {
+    ORA_EV_CG_BREAKDOWN = 0,   /* |temp2| <= SMALLFLOAT2: goto restore */
+    ORA_EV_CG_SOLSTAG,         /* ||u||_inf <= SMALLFLOAT: ERROR_SOLVER_SOLSTAG */
+    ORA_EV_CG_CHECK2,          /* check II (stagnation) entered */
+    ORA_EV_CG_CHECK2_CONV,     /* ... and its recomputed residual met the tolerance */
+    ORA_EV_CG_STAG_EXIT,       /* ... ERROR_SOLVER_STAG */
+    ORA_EV_CG_CHECK3,          /* check III (false convergence) entered */
+    ORA_EV_CG_CHECK3_CONV,     /* ... and its recomputed residual met the tolerance */
+    ORA_EV_CG_TOLSMALL_EXIT,   /* ... ERROR_SOLVER_TOLSMALL */
+    ORA_EV_CG_STAG_INC,        /* p zeroed, ++stag */
+    ORA_EV_CG_MORE_STEP_INC,   /* p zeroed, ++more_step */
+    ORA_EV_CG_BEST_COPIED,     /* the restore block copied u_best into u */
+    ORA_EV_CG_IMMEDIATE,       /* relres < tol before the first step */
+    ORA_EV_CG_MAXIT,           /* the loop ran to maxit */
+    ORA_EV_GM_IMMEDIATE,       /* relres < tol before the first Krylov cycle */
+    ORA_EV_GM_CYCLES,          /* Krylov cycles (passes of the outer loop) */
+    ORA_EV_GM_EARLY_BREAK,     /* the Arnoldi loop left by its residual estimate */
+    ORA_EV_GM_RECHECK_FAILED,  /* the true residual did not confirm the estimate: restart with i = 0 */
+    ORA_EV_GM_RECOMBINE,       /* p[0] recombined from the basis (i > 0) */
+    ORA_EV_GM_BEST_COPIED,     /* x_best copied into x at the end */
+    ORA_EV_GM_MAXIT,           /* iter >= maxit at the end */
+    ORA_EV_COUNT,              /* ---- the events end here */
+    ORA_KR_CG_STATUS = ORA_EV_COUNT,
+    ORA_KR_CG_ITER,            /* iter as the loop left it (maxit + 1 after a full run) */
+    ORA_KR_CG_ITER_BEST,
+    ORA_KR_CG_STAG,
+    ORA_KR_CG_MORE_STEP,
+    ORA_KR_GM_RAN,
+    ORA_KR_GM_STATUS,
+    ORA_KR_GM_ITER,
+    ORA_KR_COUNT
+};
+/* copies min(n, ORA_KR_COUNT) slots */
+void ora_krylov_events(int *out, int n);
+
 /* Solve/SSS_SOLVE.c:4-87; relres/absres of iterations 1..nits are stored (if non-NULL) */
 SSS_RTN ora_solve(SSS_AMG *mg, SSS_VEC *x, SSS_VEC *b, const ora_opts *o, double *relres_hist,
                   double *absres_hist, int hist_cap);
