@@ -8,6 +8,6 @@ from ._native import (  # noqa: F401
     SSS_AMG, SSS_AMG_COMP,
     SSS_AMG_PARS, SSS_HIP_OPTS, SSS_MAT, SSS_RTN, SSS_SMTR, SSS_VEC, coarse_last, csr_arrays, default_pars, device_count,
     hbm_used_bytes,
-    generate, interp_std, lib, part_save, pmis, rap_values, read_mtx, std_pattern,
+    generate, interp_exti, interp_std, lib, part_save, pmis, rap_values, read_mtx, std_pattern,
 )
 from .workloads import convdiff_csr  # noqa: F401

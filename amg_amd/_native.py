@@ -112,7 +112,7 @@ ABI_SYMBOLS = [
     "sss_hip_opts_default", "sss_hip_device_count", "sss_hip_mem_info", "sss_hip_hier_create", "sss_hip_hier_destroy",
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
     "sss_hip_rap_values", "sss_rap_values_host", "SSS_amg_refresh", "sss_hip_hier_refresh",
-    "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std",
+    "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std", "sss_hip_interp_exti",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
     "SSS_amg_save", "SSS_amg_load",
@@ -200,6 +200,7 @@ def _declare(lib):
         "sss_hip_std_pattern": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
         "sss_std_pattern_host": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
         "sss_hip_interp_std": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double]),
+        "sss_hip_interp_exti": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double]),
         "SSS_mat_struct_create": (SSS_MAT, [C.c_int, C.c_int, C.c_int]),
         "sss_hip_upload_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_download_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
@@ -394,6 +395,18 @@ def interp_std(A_csr, S_csr, mark, P_pattern, trunc: float, device: bool = False
     (row_ptr, col_idx) as std_pattern returns it.  Returns (row_ptr, col_idx, val, ncols), from the host
     (SSS_amg_interp) or from the GPU (sss_hip_interp_std).  Raises RuntimeError with the error code
     (.rc) when the device call fails."""
+    return _interp_on_pattern(A_csr, S_csr, mark, P_pattern, trunc, device, 2, "sss_hip_interp_std", "standard")
+
+
+def interp_exti(A_csr, S_csr, mark, P_pattern, trunc: float, device: bool = False):
+    """Extended+i interpolation (interp_type 3) on a pattern as std_pattern returns it:
+    the weights, the coarse renumbering of the columns and the truncation at `trunc`.  Arguments and
+    result as interp_std; from the host (SSS_amg_interp with interp_type 3) or from the GPU
+    (sss_hip_interp_exti).  Raises RuntimeError with the error code (.rc) when the device call fails."""
+    return _interp_on_pattern(A_csr, S_csr, mark, P_pattern, trunc, device, 3, "sss_hip_interp_exti", "extended+i")
+
+
+def _interp_on_pattern(A_csr, S_csr, mark, P_pattern, trunc, device, interp_type, symbol, name):
     Am = NumpyCSR(*A_csr)
     S, keep = _imat(*S_csr)
     mark = np.ascontiguousarray(mark, dtype=np.int32)
@@ -407,14 +420,14 @@ def interp_std(A_csr, S_csr, mark, P_pattern, trunc: float, device: bool = False
         C.memmove(P.col_idx, pci.ctypes.data, pci.nbytes)
     try:
         if device:
-            rc = lib().sss_hip_interp_std(C.byref(Am.mat), C.byref(S), iptr(mark), C.byref(P), trunc)
+            rc = getattr(lib(), symbol)(C.byref(Am.mat), C.byref(S), iptr(mark), C.byref(P), trunc)
             if rc != 0:
-                err = RuntimeError(f"standard interpolation failed ({rc})")
+                err = RuntimeError(f"{name} interpolation failed ({rc})")
                 err.rc = rc
                 raise err
         else:
             pars = default_pars()
-            pars.interp_type, pars.trunc_threshold = 2, trunc
+            pars.interp_type, pars.trunc_threshold = interp_type, trunc
             verts = SSS_IVEC(len(mark), iptr(mark))
             lib().SSS_amg_interp(C.byref(Am.mat), C.byref(verts), C.byref(P), C.byref(S), C.byref(pars))
         return (*csr_arrays(P), P.num_cols)

@@ -14,6 +14,12 @@
 //            are handed to the owners lane by lane, in stored order, so every slot sees its terms in
 //            the host's (j, m) order.  The scalars of the row (hat a_ii, alN, alP) are computed by
 //            every lane of the group from the same loads in the same order.
+//   ext+i    the weights of interp_type intERP_EXTI (interp_EXTI) on the same pattern, with
+//            the same table and owner rule.  The stored entries of row i are classified G at a time (one
+//            table lookup each: membership in the pattern is the lookup) and applied in stored order; a
+//            strong F neighbour k has row k of A walked twice by the group, first for den, then for the
+//            terms f a_kl, the qualifying entries of a chunk taken lane by lane from an in-order ballot.
+//            d and den are computed by every lane of the group.
 //
 // The table of a row is in LDS when the row's candidate bound (its S row plus the S rows of its strong
 // F neighbours) fits the group's share of it, else in a global array sized from the bound inside the
@@ -413,6 +419,174 @@ __global__ __launch_bounds__(kBlock) void weights_rows(Csr A, Csr S, const int *
     }
 }
 
+// the last diagonal entry of every row (0 when it has none): a_ii of interp_EXTI
+__global__ __launch_bounds__(kBlock) void exti_diag(Csr A, double *__restrict__ diag)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n) return;
+    int lo, hi;
+    span(A, i, lo, hi);
+    double d = 0.0;
+    for (int j = lo; j < hi; ++j)
+        if (A.ci[j] == i) d = A.v[j];
+    diag[i] = d;
+}
+
+// One pass of the group over row k of A for F row i: lane gl takes entry m0 + gl.  An entry (k, l)
+// qualifies when l != k, l == i or l is in the table of row i, and a_kl a_kk < 0.  Returns the group's
+// mask of qualifying lanes; val, slot (-1 for l == i) of this lane's entry.
+template <int G>
+__device__ __forceinline__ unsigned long long exti_chunk(const Csr &A, int i, int k, double akk, int m0, int khi, int gl,
+                                                         const int *key, int cap, double &val, int &slot, int *err)
+{
+    const int m = m0 + gl;
+    bool q = false;
+    val = 0.0, slot = -1;
+    if (m < khi) {
+        const int l = A.ci[m];
+        if ((unsigned)l >= (unsigned)A.n) {
+            atomicOr(err, kErrIndex);
+        } else if (l != k) {
+            val = A.v[m];
+            if (l == i) q = true;
+            else q = (slot = tab_find(key, cap, l)) >= 0;
+            q = q && val * akk < 0;
+        }
+    }
+    return group_ballot<G>(q, gl);
+}
+
+// interp_EXTI: the weights of the F rows on the pattern (fine column numbers), 1 for the C rows.  The
+// stored entries of row i are classified G at a time and applied in stored order; a strong F neighbour
+// k has row k of A walked twice by the group (den, then f a_kl to the owners or to d), the qualifying
+// entries of a chunk taken lane by lane in stored order.  d and den are computed by every lane of the
+// group from the same values in the same order.
+template <int G>
+__global__ __launch_bounds__(kBlock) void exti_rows(Csr A, Csr S, const int *__restrict__ mark, int slots,
+                                                    const int *__restrict__ need, const long long *__restrict__ goff,
+                                                    int *__restrict__ gkey, double *__restrict__ gacc,
+                                                    const int *__restrict__ prp, int pnnz, const int *__restrict__ pci,
+                                                    double *__restrict__ pv, const double *__restrict__ diag,
+                                                    int *__restrict__ err)
+{
+    __shared__ int lkey[kLdsSlots];
+    __shared__ double lacc[kLdsSlots];
+    enum { kSkip = 0, kDirect = 1, kStrongF = 2, kDiag = 3 };
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    const int i = row < A.n ? (int)row : -1;
+    const int mi = i >= 0 ? mark[i] : UNPT;
+    int *key = nullptr, cap = 0, plo = 0, phi = 0;
+    double *acc = nullptr;
+    if (mi == FGPT) {
+        plo = max(prp[i], 0);
+        phi = max(min(prp[i + 1], pnnz), plo);
+    }
+    const bool frow = mi == FGPT && phi > plo;   // an F row with an empty pattern gets nothing
+    if (frow) {
+        long long off;
+        cap = row_table(i, grp, slots, need, goff, lkey, gkey, key, off);
+        acc = off >= 0 ? gacc + off : lacc + (-1 - off);
+        for (int s = gl; s < cap; s += G) {
+            key[s] = -1;
+            acc[s] = 0.0;
+        }
+    }
+    __syncthreads();
+    if (frow)
+        for (int j = plo + gl; j < phi; j += G) {
+            const int c = pci[j];
+            if ((unsigned)c >= (unsigned)A.n) atomicOr(err, kErrIndex);
+            else if (tab_insert(key, cap, c) < 0) atomicOr(err, kErrTableFull);
+        }
+    __syncthreads();
+    double d = 0.0;
+    if (frow) {
+        int lo, hi, slo, shi;
+        span(A, i, lo, hi);
+        span(S, i, slo, shi);
+        d = diag[i];
+        // consistent input has every strong column in the row of A
+        for (int q = slo; q < shi; ++q) {
+            const int k = S.ci[q];
+            if ((unsigned)k >= (unsigned)A.n) {
+                if (gl == 0) atomicOr(err, kErrIndex);
+            } else if (group_find_last<G>(A, lo, hi, k, gl) < 0 && gl == 0) {
+                atomicOr(err, kErrStrongCol);
+            }
+        }
+        for (int j0 = lo; j0 < hi; j0 += G) {
+            const int j = j0 + gl;
+            int cls = kSkip, k = -1, slot = -1;
+            double a = 0.0;
+            if (j < hi) {
+                k = A.ci[j];
+                if ((unsigned)k >= (unsigned)A.n) {
+                    atomicOr(err, kErrIndex);
+                } else if (k != i) {
+                    a = A.v[j];
+                    slot = tab_find(key, cap, k);
+                    cls = kDiag;
+                    if (slot >= 0) {
+                        cls = kDirect;
+                    } else if (mark[k] == FGPT) {
+                        for (int q = slo; q < shi; ++q)
+                            if (S.ci[q] == k) cls = kStrongF;
+                    }
+                }
+            }
+            const int cnt = min(G, hi - j0);
+            for (int t = 0; t < cnt; ++t) {
+                const int ct = __shfl(cls, t, G);
+                if (ct == kSkip) continue;
+                const double at = __shfl(a, t, G);
+                if (ct == kDirect) {
+                    const int st = __shfl(slot, t, G);
+                    if ((st & (G - 1)) == gl) acc[st] += at;
+                } else if (ct == kDiag) {
+                    d += at;
+                } else {
+                    const int kt = __shfl(k, t, G);
+                    const double akk = diag[kt];
+                    int klo, khi, sl;
+                    double val, den = 0.0;
+                    span(A, kt, klo, khi);
+                    for (int m0 = klo; m0 < khi; m0 += G) {
+                        unsigned long long b = exti_chunk<G>(A, i, kt, akk, m0, khi, gl, key, cap, val, sl, err);
+                        for (; b; b &= b - 1) den += __shfl(val, __ffsll((long long)b) - 1, G);
+                    }
+                    if (den != 0.0) {
+                        const double f = at / den;
+                        for (int m0 = klo; m0 < khi; m0 += G) {
+                            unsigned long long b = exti_chunk<G>(A, i, kt, akk, m0, khi, gl, key, cap, val, sl, err);
+                            for (; b; b &= b - 1) {
+                                const int u = __ffsll((long long)b) - 1;
+                                const double tt = f * __shfl(val, u, G);
+                                const int su = __shfl(sl, u, G);
+                                if (su < 0) d += tt;
+                                else if ((su & (G - 1)) == gl) acc[su] += tt;
+                            }
+                        }
+                    } else {
+                        d += at;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (frow) {
+        for (int j = plo + gl; j < phi; j += G) {
+            const int c = pci[j];
+            const int slot = (unsigned)c < (unsigned)A.n ? tab_find(key, cap, c) : -1;
+            if (slot >= 0) pv[j] = -acc[slot] / d;
+        }
+    } else if (mi == CGPT && gl == 0) {
+        const int o = prp[i];
+        if ((unsigned)o < (unsigned)pnnz) pv[o] = 1.0;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void flag_coarse(int n, const int *__restrict__ mark, int *__restrict__ flag)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -626,11 +800,11 @@ int make_tables(Dev &d, Tables &t, const SSS_IMAT *S, const int *mark, const int
     return 0;
 }
 
-void timing_line(const char *step, const Dev &d, const Tables &t, int rows, int nnz)
+void timing_line(const char *step, const Dev &d, const Tables &t, int rows, int nnz, const char *rule = "standard")
 {
     if (getenv("SSS_SETUP_TIMING"))
-        fprintf(stderr, "[setup]   standard P: device %s, %d rows, %d entries, %d lanes per row, %d rows on global tables, "
-                        "copies %.4f s, kernels %.4f s\n", step, rows, nnz, t.G, t.global_rows, d.t_copy, d.t_kern);
+        fprintf(stderr, "[setup]   %s P: device %s, %d rows, %d entries, %d lanes per row, %d rows on global tables, "
+                        "copies %.4f s, kernels %.4f s\n", rule, step, rows, nnz, t.G, t.global_rows, d.t_copy, d.t_kern);
 }
 
 template <class T>
@@ -669,6 +843,11 @@ template <class... Args>
 static void launch_weights(int G, hipStream_t st, int n, Args... a)
 {
     SSS_INTERP_LAUNCH(weights_rows)
+}
+template <class... Args>
+static void launch_exti(int G, hipStream_t st, int n, Args... a)
+{
+    SSS_INTERP_LAUNCH(exti_rows)
 }
 #undef SSS_INTERP_LAUNCH
 
@@ -714,8 +893,10 @@ extern "C" int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoar
     return 0;
 }
 
-extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold)
+// the weights of interp_STD or (exti) interp_EXTI on a pattern, the coarse renumbering, the truncation
+static int interp_weights(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold, bool exti)
 {
+    const char *what = exti ? "extended+i weights" : "standard weights";
     if (!A || !P || !A->row_ptr || !P->row_ptr) return ERROR_INPUT_PAR;
     if (int rc = check_s(S, mark)) return rc;
     const int n = S->num_rows, annz = A->row_ptr[A->num_rows > 0 ? A->num_rows : 0];
@@ -729,23 +910,29 @@ extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int
     int *pci = d.upload(P->col_idx, (size_t)pnnz);
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
     Tables t;
-    if (int rc = make_tables(d, t, S, mark, prp, pnnz, "standard weights")) return rc;
+    if (int rc = make_tables(d, t, S, mark, prp, pnnz, what)) return rc;
     Csr Ad{n, annz, nullptr, nullptr, nullptr};
     Ad.rp = d.upload(A->row_ptr, (size_t)n + 1);
     Ad.ci = d.upload(A->col_idx, (size_t)annz);
     Ad.v = d.upload(A->val, (size_t)annz);
     d.lap(true);
     double *gacc = d.alloc<double>((size_t)t.total), *pv = d.alloc<double>((size_t)pnnz);
-    double *diag = d.alloc<double>((size_t)n), *csum = d.alloc<double>((size_t)n), *nsum = d.alloc<double>((size_t)n),
-           *psum = d.alloc<double>((size_t)n);
+    double *diag = d.alloc<double>((size_t)n), *csum = nullptr, *nsum = nullptr, *psum = nullptr;
+    if (!exti) csum = d.alloc<double>((size_t)n), nsum = d.alloc<double>((size_t)n), psum = d.alloc<double>((size_t)n);
     int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
     int *cnt = d.alloc<int>((size_t)n + 1), *nrp = d.alloc<int>((size_t)n + 1);
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
     SSS_HIP(hipMemsetAsync(pv, 0, sizeof(double) * (size_t)std::max(pnnz, 1), d.st));
     SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
-    hipLaunchKernelGGL(weights_sums, dim3(grid_for(n)), dim3(kBlock), 0, d.st, Ad, t.S, t.mark, diag, csum, nsum, psum, t.ctr);
-    launch_weights(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
-                   (const double *)diag, (const double *)csum, (const double *)nsum, (const double *)psum, t.ctr);
+    if (exti) {
+        hipLaunchKernelGGL(exti_diag, dim3(grid_for(n)), dim3(kBlock), 0, d.st, Ad, diag);
+        launch_exti(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
+                    (const double *)diag, t.ctr);
+    } else {
+        hipLaunchKernelGGL(weights_sums, dim3(grid_for(n)), dim3(kBlock), 0, d.st, Ad, t.S, t.mark, diag, csum, nsum, psum, t.ctr);
+        launch_weights(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
+                       (const double *)diag, (const double *)csum, (const double *)nsum, (const double *)psum, t.ctr);
+    }
     // the coarse numbers of the columns, then the truncation
     hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
     if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
@@ -754,7 +941,7 @@ extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int
                        nrp, 0, nullptr, nullptr);
     if (int rc = exclusive_sum(d, cnt, nrp, (size_t)n + 1)) return rc;
     int h_ctr[2], kept = 0, ncoarse = 0;
-    if (int rc = read_flags(d, t, "standard weights", h_ctr)) return rc;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
     if (copy_sync(&kept, nrp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
     if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
     if (kept < 0 || kept > pnnz) return ERROR_MAT_SIZE;
@@ -763,7 +950,7 @@ extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
     hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
                        nrp, kept, nci, nv);
-    if (int rc = read_flags(d, t, "standard weights", h_ctr)) return rc;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
     d.lap(false);
 
     // into arrays of its own first: P stays untouched if a copy fails
@@ -781,6 +968,16 @@ extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int
     P->row_ptr = rp.release();
     P->col_idx = ci.release();
     P->val = val.release();
-    timing_line("weights", d, t, n, kept);
+    timing_line("weights", d, t, n, kept, exti ? "extended+i" : "standard");
     return 0;
+}
+
+extern "C" int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold)
+{
+    return interp_weights(A, S, mark, P, trunc_threshold, false);
+}
+
+extern "C" int sss_hip_interp_exti(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold)
+{
+    return interp_weights(A, S, mark, P, trunc_threshold, true);
 }

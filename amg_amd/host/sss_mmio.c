@@ -345,6 +345,9 @@ void SSS_amg_pars_init(SSS_AMG_PARS *pars)
         pars->cs_type = SSS_COARSE_PMIS;
         pars->interp_type = intERP_STD;
     }
+    /* SSS_SETUP_INTERP=exti, read after the split's choice: the extended+i weights on the same pattern */
+    const char *it = getenv("SSS_SETUP_INTERP");
+    if (it && strcmp(it, "exti") == 0) pars->interp_type = intERP_EXTI;
 }
 
 /* SSS_main.c:67-119 — byte-identical stdout. */
@@ -372,6 +375,8 @@ void SSS_amg_pars_print(SSS_AMG_PARS *pars)
         printf("AMG interPolation type:            Dir\n");
     else if (pars->interp_type == intERP_STD)
         printf("AMG interPolation type:            STD\n");
+    else if (pars->interp_type == intERP_EXTI)
+        printf("AMG interPolation type:            EXTI\n");
     printf("AMG dof on coarsest grid:          %d\n", pars->coarse_dof);
     printf("AMG strong threshold:              %.4lf\n", pars->strong_threshold);
     printf("AMG truncation threshold:          %.4lf\n", pars->trunc_threshold);

@@ -20,7 +20,9 @@
  * amg_amd/csrc/sss_pmis.hip).  No F-F cleanup runs after it; interp_type 2 is its partner.  With
  * cs_type 1 nothing here differs from the reference.  On large levels the standard pattern and
  * interpolation run on the device (sss_hip_std_pattern, sss_hip_interp_std, amg_amd/csrc/sss_interp.hip):
- * the same P bit for bit, with the code below as the fallback.
+ * the same P bit for bit, with the code below as the fallback.  A second extension, interp_type
+ * intERP_EXTI (3): the extended+i weights on the standard pattern (interp_EXTI below; on the device
+ * sss_hip_interp_exti, the same file).
  *
  * The measure lists are kept as an array of FIFO buckets indexed by measure instead of the
  * reference's heap-allocated sorted list of list nodes with element-level linked lists
@@ -792,7 +794,8 @@ int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS
         if (timing)
             fprintf(stderr, "[setup]   coarsen: strength %.3f s, %s split %.3f s, F-F cleanup %.3f s, P pattern %.3f s\n",
                     t1 - t0, split, t2 - t1, t3 - t2, SSS_get_time() - t3);
-    } else if (pars->interp_type == intERP_STD) {   /* no F-F cleanup before the standard pattern */
+    } else if (pars->interp_type == intERP_STD || pars->interp_type == intERP_EXTI) {
+        /* no F-F cleanup before the standard pattern; the extended+i weights use the same pattern */
         const double t3 = SSS_get_time();
         /* the device pattern is the host's, array for array; on any error code the host builds it */
         if (!(interp_on_device(A->num_nnzs) && sss_hip_std_pattern(S, vertices->d, ncoarse, P) == 0)) {
@@ -1128,10 +1131,119 @@ static void interp_STD(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, 
                 P->num_nnzs);
 }
 
+/*
+ * Extended+i interpolation (interp_type intERP_EXTI, an engine extension; De Sterck, Falgout, Nolting,
+ * Yang 2008) on the pattern std_pattern built.  Per F row i with pattern C_i, d = a_ii
+ * (the row's last diagonal entry) and hat a = 0, the stored entries (i, k), k != i, in stored order:
+ *   k in C_i (strongly or weakly coupled) ............ hat a_k += a_ik
+ *   k a strong F neighbour (k in S_i, mark F) ........ over the entries (k, l), l != k, of row k with
+ *       l in C_i or l == i, and a_kl a_kk < 0, in stored order: den = sum a_kl; when den != 0,
+ *       f = a_ik / den and f a_kl goes to d (l == i) or to hat a_l; when den == 0, d += a_ik
+ *   anything else ..................................... d += a_ik
+ *   p_ic = -hat a_c / d
+ * There is no alpha: a strong F neighbour is eliminated through the part of its row inside
+ * C_i u {i}, so a row of A with zero sum gives a row of P with sum 1.  Rows are independent (per-thread
+ * scratch: hat a, and two arrays stamped with the row for "in C_i" and "in S_i").  Then the coarse
+ * renumbering and the truncation, as interp_STD.
+ */
+static void interp_EXTI(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
+{
+    const int n = A->num_rows, nc = A->num_cols > n ? A->num_cols : n;
+    const int *mark = vertices->d;
+    const int *ia = A->row_ptr, *ja = A->col_idx;
+    const double *a = A->val;
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const double t0 = SSS_get_time();
+    /* the device weights (renumbered, truncated) are the host's bit for bit; on any error code P is
+     * untouched and the host computes them */
+    if (interp_on_device(A->num_nnzs) && sss_hip_interp_exti(A, S, mark, P, pars->trunc_threshold) == 0) return;
+    double *diag = (double *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(double));
+#pragma omp parallel for schedule(static) if (n > 65536)
+    for (int i = 0; i < n; ++i) {
+        double d = 0.0;
+        for (int j = ia[i]; j < ia[i + 1]; ++j)
+            if (ja[j] == i) d = a[j];
+        diag[i] = d;
+    }
+
+    /* per thread: ahat (doubles), inpat and ins (ints), nc each, in one buffer */
+    void *scr[kScratchMax];
+    const size_t ncs = (size_t)(nc > 0 ? nc : 1);
+    const int T = scratch_alloc(ncs * (2 * sizeof(int) + sizeof(double)), scr);
+#pragma omp parallel num_threads(T) if (n > 4096)
+    {
+        double *ahat = (double *)scr[omp_get_thread_num()];
+        int *inpat = (int *)(ahat + ncs), *ins = inpat + ncs;
+        for (size_t c = 0; c < ncs; ++c) inpat[c] = ins[c] = -1;
+#pragma omp for schedule(dynamic, 1024)
+        for (int i = 0; i < n; ++i) {
+            if (mark[i] == CGPT) {
+                P->val[P->row_ptr[i]] = 1.0;
+                continue;
+            }
+            if (mark[i] != FGPT || P->row_ptr[i + 1] == P->row_ptr[i]) continue;
+            double d = diag[i];
+            for (int j = P->row_ptr[i]; j < P->row_ptr[i + 1]; ++j) {
+                ahat[P->col_idx[j]] = 0.0;
+                inpat[P->col_idx[j]] = i;
+            }
+            for (int j = S->row_ptr[i]; j < S->row_ptr[i + 1]; ++j) ins[S->col_idx[j]] = i;
+            for (int j = ia[i]; j < ia[i + 1]; ++j) {
+                const int k = ja[j];
+                if (k == i) continue;
+                const double aik = a[j];
+                if (inpat[k] == i) {
+                    ahat[k] += aik;
+                } else if (ins[k] == i && mark[k] == FGPT) {
+                    const double akk = diag[k];
+                    double den = 0.0;
+                    for (int m = ia[k]; m < ia[k + 1]; ++m) {
+                        const int l = ja[m];
+                        if (l != k && (l == i || inpat[l] == i) && a[m] * akk < 0) den += a[m];
+                    }
+                    if (den != 0.0) {
+                        const double f = aik / den;
+                        for (int m = ia[k]; m < ia[k + 1]; ++m) {
+                            const int l = ja[m];
+                            if (l != k && (l == i || inpat[l] == i) && a[m] * akk < 0) {
+                                const double t = f * a[m];
+                                if (l == i) d += t;
+                                else ahat[l] += t;
+                            }
+                        }
+                    } else {
+                        d += aik;
+                    }
+                } else {
+                    d += aik;
+                }
+            }
+            for (int j = P->row_ptr[i]; j < P->row_ptr[i + 1]; ++j) P->val[j] = -ahat[P->col_idx[j]] / d;
+        }
+    }
+    scratch_free(scr, T);
+
+    /* coarse renumbering of the columns, then the truncation */
+    int *cmap = (int *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(int));
+    int ncoarse = 0;
+    for (int i = 0; i < n; ++i)
+        if (mark[i] == CGPT) cmap[i] = ncoarse++;
+    P->num_cols = ncoarse;
+#pragma omp parallel for schedule(static) if (P->num_nnzs > 65536)
+    for (int q = 0; q < P->row_ptr[P->num_rows]; ++q) P->col_idx[q] = cmap[P->col_idx[q]];
+    free(cmap);
+    free(diag);
+    SSS_amg_interp_trunc(P, pars);
+    if (timing)
+        fprintf(stderr, "[setup]   extended+i P: host weights %.4f s, %d rows, %d entries\n", SSS_get_time() - t0, P->num_rows,
+                P->num_nnzs);
+}
+
 void SSS_amg_interp(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
 {
     if (pars->interp_type == intERP_DIR) interp_DIR(A, vertices, P, pars);
     else if (pars->interp_type == intERP_STD) interp_STD(A, vertices, P, S, pars);
+    else if (pars->interp_type == intERP_EXTI) interp_EXTI(A, vertices, P, S, pars);
     else SSS_exit_on_errcode(ERROR_AMG_interp_type, __func__);
 }
 

@@ -111,7 +111,10 @@ typedef enum SSS_SM_TYPE_ {        /* SSS_main.h:133-145 */
     SSS_SM_L1DIAG = 9
 } SSS_SM_TYPE;
 
-typedef enum interp_type_ { intERP_DIR = 1, intERP_STD = 2 } interp_type;   /* SSS_main.h:147-152 */
+/* 1 and 2 are the reference's (SSS_main.h:147-152); intERP_EXTI is an engine extension: the extended+i
+ * interpolation (De Sterck, Falgout, Nolting, Yang 2008) on the pattern of intERP_STD, the partner of
+ * SSS_COARSE_PMIS.  SSS_SETUP_INTERP=exti makes SSS_amg_pars_init choose it. */
+typedef enum interp_type_ { intERP_DIR = 1, intERP_STD = 2, intERP_EXTI = 3 } interp_type;
 
 typedef struct SSS_RTN_ {          /* SSS_main.h:154-160; sizeof 24 */
     double ares;

@@ -170,6 +170,20 @@ int sss_pmis_host(const SSS_IMAT *S, int *mark, int *ncoarse, int *rounds);
 #define SSS_SETUP_GPU_INTERP_MIN_DEFAULT 10000000
 int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P);
 int sss_hip_interp_std(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold);
+/* The extended+i interpolation (interp_type intERP_EXTI, an engine extension) on the GPU,
+ * bit for bit the host's interp_EXTI, on a pattern as sss_hip_std_pattern builds it.  Per F row i with
+ * pattern C_i, d = a_ii and hat a = 0, the stored entries (i, k), k != i, in stored order: k in C_i adds
+ * a_ik to hat a_k; a strong F neighbour k (k in S_i, marked F) is eliminated through the entries (k, l)
+ * of its row with l in C_i or l == i and a_kl a_kk < 0 (den their sum in stored order: f = a_ik / den,
+ * f a_kl goes to d for l == i and to hat a_l otherwise; den == 0 adds a_ik to d); anything else adds
+ * a_ik to d; p_ic = -hat a_c / d.  No alpha.  Then the coarse renumbering of the columns and the
+ * truncation; P's arrays are freed and replaced.  The contract, the switches (SSS_HIP_INTERP_LANES,
+ * SSS_HIP_INTERP_LDS_SLOTS, SSS_SETUP_GPU_INTERP, SSS_SETUP_GPU_INTERP_MIN) and the SSS_SETUP_TIMING line
+ * are those of sss_hip_interp_std.  Returns 0, or an error code with P untouched: ERROR_INPUT_PAR (a NULL
+ * or misshapen argument), ERROR_MAT_SIZE (too many rows for the grid), ERROR_MISC (no device, a failed
+ * HIP call or copy), ERROR_DATA_STRUCTURE (input the kernels found inconsistent: an index out of range, a
+ * strong column absent from the row of A, a full table); the setup then runs the host code. */
+int sss_hip_interp_exti(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold);
 /* The pattern on the host (OpenMP, row-parallel): what the setup runs without a device or on small
  * levels, and what the device pattern is tested against.  0 or an error code. */
 int sss_std_pattern_host(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P);
