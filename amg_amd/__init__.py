@@ -7,7 +7,7 @@ from ._native import (  # noqa: F401
     ABI_SYMBOLS, COARSE, COARSE_LAST_FIELDS, COARSE_PMIS, COARSE_RS, SMOOTH, SPMV, Comm, DeviceHierarchy, DistHierarchy, Hierarchy, NumpyCSR, PartPlan,
     SSS_AMG, SSS_AMG_COMP,
     SSS_AMG_PARS, SSS_HIP_OPTS, SSS_MAT, SSS_RTN, SSS_SMTR, SSS_VEC, coarse_last, csr_arrays, default_pars, device_count,
-    hbm_used_bytes,
+    hbm_used_bytes, level_step, spmv_enc,
     generate, interp_exti, interp_std, lib, part_save, pmis, rap_values, read_mtx, std_pattern,
 )
 from .workloads import convdiff_csr  # noqa: F401

@@ -90,6 +90,21 @@ class SSS_HIP_LEVEL_INFO(C.Structure):
                 ("inner", C.c_int), ("r_format", C.c_int), ("p_format", C.c_int), ("pad_", C.c_int)]
 
 
+class SSS_HIP_STORE_INFO(C.Structure):
+    _fields_ = [("a_format", C.c_int), ("ell_w", C.c_int), ("xell_w", C.c_int), ("xell_shift", C.c_int),
+                ("ell_based", C.c_int), ("nblk", C.c_int), ("split_blk", C.c_int), ("pad_", C.c_int)]
+
+
+#: SSS_HIP_ENC_*: the storage formats an upload may take (sss_hip_host_spmv_enc, sss_hip_host_level_step)
+ENC_SORTED_TILES, ENC_FREE_ORDER, ENC_DICT, ENC_MERGED_ONLY, ENC_XELL, ENC_ELL, ENC_ELL_BASE = 1, 2, 4, 8, 16, 32, 64
+#: a_format bits (sss_hip_level_info, sss_hip_store_info)
+FMT_SORTED, FMT_DICT, FMT_FREE, FMT_MERGED, FMT_WAVE, FMT_ELL, FMT_XELL = 1, 2, 4, 8, 16, 64, 128
+#: the ints of sss_hip_host_level_step's plan_info, in order (SSS_HIP_PI_*)
+PLAN_INFO_FIELDS = ("range_f", "range_c", "fused", "pend_ok", "inner", "nl_f_format", "nl_f_xell_w", "lo_f_format",
+                    "lo_f_xell_w", "nl_c_format", "nl_c_xell_w", "lo_c_format", "lo_c_xell_w", "stall", "fuse_resid",
+                    "f_overwritten")
+STEP_NO_PEND = 1
+
 SMOOTH = {"exact": 0, "hybrid": 1, "jacobi": 2}
 #: SSS_COARSEN_TYPE values of SSS_AMG_PARS.cs_type (3 is an engine extension, the parallel split)
 COARSE_RS, COARSE_PMIS = 1, 3
@@ -120,6 +135,7 @@ ABI_SYMBOLS = [
     "sss_hip_cycle_launches", "sss_hip_cycle_bytes",
     "sss_hip_merged_narrow", "sss_hip_merged_key_stats", "sss_hip_merged_keys_get",
     "sss_hip_spmv_plan_create", "sss_hip_spmv_plan_destroy", "sss_hip_spmv", "sss_hip_host_spmv", "sss_hip_host_spmv_order",
+    "sss_hip_host_spmv_enc", "sss_hip_host_level_step",
     "sss_hip_host_smooth", "sss_hip_host_coarse_solve", "sss_hip_host_cache_clear", "sss_hip_time_level0_spmv", "sss_hip_time_iterations",
     "sss_hip_time_level0_spmv_csr", "sss_hip_time_levels", "sss_hip_dist_time_tail_levels",
     "sss_gen_stencil",
@@ -230,6 +246,10 @@ def _declare(lib):
         "sss_hip_merged_keys_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
         "sss_hip_host_spmv": (C.c_int, [C.c_int, C.c_double, P(SSS_MAT), _dbl_p, _dbl_p, _dbl_p, C.c_int]),
         "sss_hip_host_spmv_order": (C.c_int, [C.c_int, C.c_double, P(SSS_MAT), _dbl_p, _dbl_p, _dbl_p, C.c_int, C.c_int]),
+        "sss_hip_host_spmv_enc": (C.c_int, [C.c_int, C.c_double, P(SSS_MAT), _dbl_p, _dbl_p, _dbl_p, C.c_int, C.c_int,
+                                            C.c_int, P(SSS_HIP_STORE_INFO)]),
+        "sss_hip_host_level_step": (C.c_int, [P(SSS_MAT), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              _dbl_p, _dbl_p, _dbl_p, _dbl_p, P(SSS_HIP_STORE_INFO), _int_p]),
         "sss_hip_host_smooth": (C.c_int, [P(SSS_SMTR), C.c_int]),
         "sss_hip_host_coarse_solve": (C.c_int, [P(SSS_MAT), P(SSS_VEC), P(SSS_VEC), C.c_double, C.c_int,
                                                 C.c_int]),
@@ -671,6 +691,47 @@ class DeviceHierarchy:
             self.close()
         except Exception:
             pass
+
+
+def _store_info(info: SSS_HIP_STORE_INFO) -> dict:
+    return {k: getattr(info, k) for k, _ in SSS_HIP_STORE_INFO._fields_ if k != "pad_"}
+
+
+def spmv_enc(op: str, alpha: float, M: SSS_MAT, x, b, y, cap: int, enc: int, split: int = -1):
+    """One SpMV op (SPMV) of M stored as an upload with the ENC_* flags `enc` and the class split row
+    `split` stores it (sss_hip_host_spmv_enc): (the new y, what the upload chose)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.array(y, dtype=np.float64)
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    info = SSS_HIP_STORE_INFO()
+    rc = lib().sss_hip_host_spmv_enc(SPMV[op], alpha, C.byref(M), dptr(x), None if b is None else dptr(b), dptr(y), cap,
+                                     enc, split, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"sss_hip_host_spmv_enc failed ({rc})")
+    return y, _store_info(info)
+
+
+def level_step(M: SSS_MAT, nF: int, enc: int, kind: str, inner: int, sweeps: int, post: bool, fuse: int, b, x,
+               resid: bool = True):
+    """One smoother call on M as a relabeled level (rows [0, nF) class F, the rest class C) stored with
+    the ENC_* flags `enc` (sss_hip_host_level_step): (x, r, rnorm2, store info, plan info); r and
+    rnorm2 are None without `resid` (fuse 0 only), and x is None where fuse 2 does not apply."""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    x = np.array(x, dtype=np.float64)
+    n = M.num_rows
+    r = np.zeros(n) if (resid or fuse) else None
+    rn = C.c_double(0.0)
+    info = SSS_HIP_STORE_INFO()
+    pi = (C.c_int * len(PLAN_INFO_FIELDS))()
+    rc = lib().sss_hip_host_level_step(C.byref(M), nF, enc, SMOOTH[kind], inner, sweeps, int(post), fuse, dptr(b), dptr(x),
+                                       None if r is None else dptr(r), None if r is None else C.byref(rn),
+                                       C.byref(info), pi)
+    plan = dict(zip(PLAN_INFO_FIELDS, pi))
+    if rc == STEP_NO_PEND:
+        return None, None, None, _store_info(info), plan
+    if rc != 0:
+        raise RuntimeError(f"sss_hip_host_level_step failed ({rc})")
+    return x, r, (None if r is None else rn.value), _store_info(info), plan
 
 
 def hbm_used_bytes() -> int:

@@ -1533,6 +1533,13 @@ extern "C" int sss_hip_cycle_launches(sss_hip_hier *h)
     return h->cycle_graph_ready_p ? h->cycle_kernels_p : h->cycle_kernels;
 }
 
+// the a_format bits of sss_hip_level_info / sss_hip_store_info
+static int format_bits(const DevCSR &M)
+{
+    return (M.pk ? 1 : 0) | (has_dict(M) ? 2 : 0) | (M.vec_rows ? 4 : 0) | (M.mg_G ? 8 : 0) | (M.wave_rows ? 16 : 0) |
+           (M.dv_ell ? 64 : 0) | (M.dv_xell ? 128 : 0);
+}
+
 extern "C" int sss_hip_level_info_get(sss_hip_hier *h, int level, sss_hip_level_info *out)
 {
     if (!h || level < 0 || level >= h->nl) return ERROR_INPUT_PAR;
@@ -1551,13 +1558,9 @@ extern "C" int sss_hip_level_info_get(sss_hip_hier *h, int level, sss_hip_level_
     if (L.sm.fz.err && hipMemcpy(&ez, L.sm.fz.err, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
         return ERROR_MISC;
     out->gs_stall = (int)(ef | ec | ez);
-    auto fmt = [](const DevCSR &M) {
-        return (M.pk ? 1 : 0) | (has_dict(M) ? 2 : 0) | (M.vec_rows ? 4 : 0) | (M.mg_G ? 8 : 0) | (M.wave_rows ? 16 : 0) |
-               (M.dv_ell ? 64 : 0) | (M.dv_xell ? 128 : 0);
-    };
-    out->a_format = fmt(L.A);
-    out->r_format = level + 1 < h->nl ? fmt(L.R) : 0;
-    out->p_format = level + 1 < h->nl ? fmt(L.P) : 0;
+    out->a_format = format_bits(L.A);
+    out->r_format = level + 1 < h->nl ? format_bits(L.R) : 0;
+    out->p_format = level + 1 < h->nl ? format_bits(L.P) : 0;
     out->a_stream_bytes = L.A.stream_bytes;
     return 0;
 }
@@ -1940,6 +1943,149 @@ extern "C" int sss_hip_host_smooth(const SSS_SMTR *s, int post)
     if (stalled && !rc) rc = stall_error("SSS_amg_smoother_pre/post");
     dev_free(dx);
     dev_free(db);
+    return rc;
+}
+
+// ---- one matrix in a chosen storage format (tests/test_gpu_format_edges.py) ---------------------
+static_assert(SSS_HIP_ENC_SORTED_TILES == kEncSortedTiles, "SSS_HIP_ENC_SORTED_TILES");
+static_assert(SSS_HIP_ENC_FREE_ORDER == kEncFreeOrder, "SSS_HIP_ENC_FREE_ORDER");
+static_assert(SSS_HIP_ENC_DICT == kEncDict, "SSS_HIP_ENC_DICT");
+static_assert(SSS_HIP_ENC_MERGED_ONLY == kEncMergedOnly, "SSS_HIP_ENC_MERGED_ONLY");
+static_assert(SSS_HIP_ENC_XELL == kEncXell, "SSS_HIP_ENC_XELL");
+static_assert(SSS_HIP_ENC_ELL == kEncEll, "SSS_HIP_ENC_ELL");
+static_assert(SSS_HIP_ENC_ELL_BASE == kEncEllBase, "SSS_HIP_ENC_ELL_BASE");
+
+static void store_info_of(const DevCSR &M, sss_hip_store_info *o)
+{
+    if (!o) return;
+    o->a_format = format_bits(M);
+    o->ell_w = M.dv_ell ? M.ell_w : 0;
+    o->xell_w = M.dv_xell ? M.xell_w : 0;
+    o->xell_shift = M.dv_xell ? M.xell_shift : 0;
+    o->ell_based = M.dv_ell_base ? 1 : 0;
+    o->nblk = M.nblk;
+    o->split_blk = M.split_blk;
+    o->pad_ = 0;
+}
+
+// the caller's flags under the switches that act on the flags themselves (the others act inside the upload)
+static int switched_encoding(int enc)
+{
+    sss_hip_opts o;
+    sss_hip_opts_default(&o);   // SSS_HIP_SORTED_TILES
+    if (!o.sorted_tiles) enc &= ~kEncSortedTiles;
+    if (!upload_switches().ell_base) enc &= ~kEncEllBase;   // SSS_HIP_ELL_BASE (restriction_encoding)
+    return enc;
+}
+
+namespace {
+// device vectors of one call, released with it
+struct DevVecs {
+    std::vector<void *> p;
+    int rc = 0;
+    double *get(size_t count, const double *src = nullptr)   // src: count doubles copied in
+    {
+        double *d = dev_alloc<double>(count);
+        p.push_back(d);
+        if (!d) rc = rc ? rc : ERROR_ALLOC_MEM;
+        else if (src && count > 0 && hipMemcpy(d, src, sizeof(double) * count, hipMemcpyHostToDevice) != hipSuccess)
+            rc = rc ? rc : ERROR_MISC;
+        return d;
+    }
+    ~DevVecs()
+    {
+        for (void *q : p) dev_free(q);
+    }
+};
+}  // namespace
+
+extern "C" int sss_hip_host_spmv_enc(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
+                                     double *y, int cap, int enc, int split, sss_hip_store_info *info)
+{
+    if (!A || !x || !y || (op == SSS_HIP_SPMV_RESID && !b)) return ERROR_INPUT_PAR;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    enc = switched_encoding(enc);
+    HostCSR M;
+    if (devcsr_upload(M.d, *A, split, enc)) return ERROR_MISC;
+    store_info_of(M.d, info);
+    const size_t ny = (size_t)A->num_rows, nx = (size_t)A->num_cols;
+    DevVecs dv;
+    double *dx = dv.get(nx, x), *dy = dv.get(ny, y), *db = dv.get(ny, b);
+    int rc = dv.rc;
+    if (!rc) rc = launch_spmv(M.d, op, alpha, dx, db, dy, cap, nullptr, nullptr);
+    if (!rc && hipMemcpy(y, dy, sizeof(double) * ny, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
+    return rc;
+}
+
+extern "C" int sss_hip_host_level_step(const SSS_MAT *A, int nF, int enc, int kind, int inner, int sweeps, int post,
+                                       int fuse, const double *b, double *x, double *r, double *rnorm2,
+                                       sss_hip_store_info *info, int *plan_info)
+{
+    if (!A || !b || !x || !plan_info || A->num_rows != A->num_cols || nF < 0 || nF > A->num_rows || sweeps < 0 ||
+        inner < 0 || fuse < 0 || fuse > 2 || (kind != SSS_HIP_SMOOTH_EXACT && kind != SSS_HIP_SMOOTH_JACOBI) ||
+        (fuse > 0 && (!r || !rnorm2)) || (!r != !rnorm2))
+        return ERROR_INPUT_PAR;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    const int n = A->num_rows;
+    enc = switched_encoding(enc);
+    for (int i = 0; i < SSS_HIP_PLAN_INFO_N; ++i) plan_info[i] = 0;
+    HostSmooth M;
+    if (devcsr_upload(M.d, *A, nF, enc)) return ERROR_MISC;
+    store_info_of(M.d, info);
+    std::vector<int> mark((size_t)std::max(n, 1));
+    for (int i = 0; i < n; ++i) mark[i] = i < nF ? 0 : 1;   // 1 = C (classes_independent)
+    if (smoother_build(M.sp, *A, mark.data(), kind, &M.d, inner, nullptr, enc)) return ERROR_MISC;
+    if (M.sp.inner == 0 && devcsr_sort_rows(M.d, *A)) return ERROR_MISC;   // plain passes read A's rows
+    const SmootherPlan &sp = M.sp;
+    plan_info[SSS_HIP_PI_RANGE_F] = sp.pass[0].range;
+    plan_info[SSS_HIP_PI_RANGE_C] = sp.pass[1].range;
+    plan_info[SSS_HIP_PI_PEND_OK] = sp.pend_ok;
+    plan_info[SSS_HIP_PI_INNER] = sp.inner;
+    plan_info[SSS_HIP_PI_FUSE_RESID] = sp.fuse_resid;
+    plan_info[SSS_HIP_PI_F_OVERWRITTEN] = sp.f_overwritten;
+    for (int c = 0; c < 2; ++c) {
+        const DevCSR *copy[2] = {&sp.pass[c].ts_nl, &sp.pass[c].ts_lo};
+        for (int w = 0; w < 2; ++w) {
+            plan_info[SSS_HIP_PI_NL_F_FORMAT + 4 * c + 2 * w] = format_bits(*copy[w]);
+            plan_info[SSS_HIP_PI_NL_F_XELL_W + 4 * c + 2 * w] = copy[w]->dv_xell ? copy[w]->xell_w : 0;
+        }
+    }
+    if (fuse == 2 && !sp.pend_ok) return SSS_HIP_STEP_NO_PEND;
+    DevVecs dv;
+    double *dx = dv.get((size_t)n, x), *db = dv.get((size_t)n, b);
+    double *dr = r ? dv.get((size_t)n) : nullptr;
+    double *partial = r ? dv.get((size_t)M.d.ngrid + kFinalScratch) : nullptr, *dsum = r ? dv.get(1) : nullptr;
+    double *pend = fuse == 2 ? dv.get((size_t)n) : nullptr;
+    int rc = dv.rc;
+    if (!rc && r && hipMemset(dr, 0, sizeof(double) * (size_t)n) != hipSuccess) rc = ERROR_MISC;
+    ResidFuse rf;
+    rf.r = dr;
+    rf.partial = partial;
+    if (!rc && fuse == 2) rc = launch_f_residual_pending(sp, M.d, db, dx, dr, partial, pend, nullptr);
+    if (!rc)
+        rc = smoother_run(sp, M.d, db, dx, sweeps, nullptr, nullptr, fuse ? &rf : nullptr, pend, false, post != 0);
+    plan_info[SSS_HIP_PI_FUSED] = rf.done;
+    if (!rc && r) {
+        rc = rf.done ? launch_spmv_blocks(M.d, M.d.split_blk, SSS_HIP_SPMV_RESID, -1.0, dx, db, dr, partial, nullptr)
+                     : launch_spmv(M.d, SSS_HIP_SPMV_RESID, -1.0, dx, db, dr, 0, partial, nullptr);
+        if (!rc) rc = launch_final_sum(partial, M.d.ngrid, dsum, false, nullptr);
+    }
+    if (!rc && hipDeviceSynchronize() != hipSuccess) rc = ERROR_MISC;
+    if (!rc && hipMemcpy(x, dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = ERROR_MISC;
+    if (!rc && r && (hipMemcpy(r, dr, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+                     hipMemcpy(rnorm2, dsum, sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+        rc = ERROR_MISC;
+    // the stall words, read and cleared as sss_hip_host_smooth does
+    unsigned stall = 0;
+    for (auto &ps : M.sp.pass) {
+        unsigned e = 0;
+        if (gs_persist_error(ps, &e)) rc = rc ? rc : ERROR_MISC;
+        if (e) (void)hipMemset(ps.gp.err, 0, sizeof(unsigned));
+        stall |= e;
+    }
+    unsigned ez = 0;
+    if (gs_fused_error(M.sp.fz, &ez, true)) rc = rc ? rc : ERROR_MISC;
+    plan_info[SSS_HIP_PI_STALL] = (int)(stall | ez);
     return rc;
 }
 

@@ -343,6 +343,68 @@ int sss_hip_host_spmv(int op, double alpha, const SSS_MAT *A, const double *x, c
 int sss_hip_host_spmv_order(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
                             double *y, int cap, int sum_order);
 int sss_hip_host_smooth(const SSS_SMTR *s, int post);
+
+/* ---- one matrix in a chosen storage format (tests of the formats at their limits) ----- */
+/* The encoding flags of a matrix upload: which storage formats it may take (those it qualifies for
+ * are tried in the order dictionary ELL, column ELL, dictionary tiles, sorted tiles with or without
+ * value dictionaries; the SSS_HIP_DICT / ELL / ELL_BASE / XELL switches still apply). */
+enum {
+    SSS_HIP_ENC_SORTED_TILES = 1,   /* column-sorted tile staging */
+    SSS_HIP_ENC_FREE_ORDER = 2,     /* free summation order on long-row matrices */
+    SSS_HIP_ENC_DICT = 4,           /* the dictionary formats (square: dictionary ELL, dictionary tiles;
+                                       value dictionaries over the sorted tiles) */
+    SSS_HIP_ENC_MERGED_ONLY = 8,    /* read through a merged copy / no range relaxation: column ELL up to
+                                       40 slots per row */
+    SSS_HIP_ENC_XELL = 16,          /* column ELL */
+    SSS_HIP_ENC_ELL = 32,           /* dictionary ELL also for a rectangular matrix, no dictionary tiles */
+    SSS_HIP_ENC_ELL_BASE = 64       /* rectangular: dictionary ELL with offsets against each row's first column */
+};
+/* What an upload chose: the a_format bits of sss_hip_level_info, the row widths of the dictionary ELL
+ * and the column ELL (0: not taken), the column bits of a column ELL code, whether the dictionary
+ * ELL has per-row bases, the row blocks and the block that starts at the class split. */
+typedef struct sss_hip_store_info {
+    int a_format, ell_w, xell_w, xell_shift, ell_based, nblk, split_blk, pad_;
+} sss_hip_store_info;
+/* sss_hip_host_spmv with the upload's encoding flags and class split row (-1: none) given by the
+ * caller, on a device object built for this call alone (never cached); *info receives what the
+ * upload chose. */
+int sss_hip_host_spmv_enc(int op, double alpha, const SSS_MAT *A, const double *x, const double *b,
+                          double *y, int cap, int enc, int split, sss_hip_store_info *info);
+/* One smoother call of a level on host data.  A is laid out as a relabeled level: rows [0, nF) are
+ * class F, rows [nF, n) class C.  It is uploaded with a block split at nF and the flags enc, and
+ * smoothed by `sweeps` sweeps of `kind` (SSS_HIP_SMOOTH_EXACT or _JACOBI; `inner` two-stage steps),
+ * x in place, on a device object built for this call alone.
+ *   fuse 0: the smoother alone; then (r and rnorm2 given) r = b - A x by a residual SpMV.
+ *   fuse 1: the smoother with the C rows' residual fused into its last pass where the plan allows,
+ *           the F rows' (or the whole) residual after it, as the cycle's descent does.
+ *   fuse 2: the F rows' residual of the incoming x together with the first F pass, then as fuse 1
+ *           with that pass skipped (the cycle after an outer residual); SSS_HIP_STEP_NO_PEND, with
+ *           nothing run, where the plan does not allow it.
+ * r (n doubles) and *rnorm2 (the sum of squares of r, per-block partials summed in a fixed order)
+ * are optional with fuse 0.  plan_info receives SSS_HIP_PLAN_INFO_N ints (SSS_HIP_PI_*). */
+enum { SSS_HIP_STEP_NO_PEND = 1 };
+enum {
+    SSS_HIP_PI_RANGE_F = 0,   /* the F / C pass runs on the level matrix's own row blocks */
+    SSS_HIP_PI_RANGE_C,
+    SSS_HIP_PI_FUSED,         /* the last C pass wrote its rows' residual */
+    SSS_HIP_PI_PEND_OK,       /* the plan allows fuse 2 */
+    SSS_HIP_PI_INNER,         /* two-stage inner steps of the plan (0: none) */
+    SSS_HIP_PI_NL_F_FORMAT,   /* a_format bits and column ELL width of the two-stage copies: */
+    SSS_HIP_PI_NL_F_XELL_W,   /*   the F class's [N | L] rows, */
+    SSS_HIP_PI_LO_F_FORMAT,   /*   its L rows, */
+    SSS_HIP_PI_LO_F_XELL_W,
+    SSS_HIP_PI_NL_C_FORMAT,   /*   the C class's [N | L] rows, */
+    SSS_HIP_PI_NL_C_XELL_W,
+    SSS_HIP_PI_LO_C_FORMAT,   /*   its L rows */
+    SSS_HIP_PI_LO_C_XELL_W,
+    SSS_HIP_PI_STALL,         /* the one-launch passes' stall words, or-ed (read and cleared) */
+    SSS_HIP_PI_FUSE_RESID,    /* the plan can fuse the C rows' residual */
+    SSS_HIP_PI_F_OVERWRITTEN, /* the F pass overwrites x_F from C values only */
+    SSS_HIP_PLAN_INFO_N
+};
+int sss_hip_host_level_step(const SSS_MAT *A, int nF, int enc, int kind, int inner, int sweeps, int post,
+                            int fuse, const double *b, double *x, double *r, double *rnorm2,
+                            sss_hip_store_info *info, int *plan_info);
 /* One orthogonalisation step of sss_hip_fgmres on host data, through the same kernels: V holds k
  * columns of n doubles back to back; w is orthogonalised against them in place (not normalised),
  * hcol[0 .. k) receives the Hessenberg coefficients and *norm the 2-norm of the new w. */
