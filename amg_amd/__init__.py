@@ -4,10 +4,10 @@ The product is the C-ABI library ``amg_amd/lib/libsss_amg.so`` (host C + gfx950 
 and the ``amg_amd/bin/amg`` CLI; this package is the Python binding used by tests and bench.py.
 """
 from ._native import (  # noqa: F401
-    ABI_SYMBOLS, COARSE, COARSE_LAST_FIELDS, COARSE_PMIS, COARSE_RS, SMOOTH, SPMV, Comm, DeviceHierarchy, DistHierarchy, Hierarchy, NumpyCSR, PartPlan,
+    ABI_SYMBOLS, COARSE, COARSE_LAST_FIELDS, COARSE_PMIS, COARSE_PMIS_AGG, COARSE_RS, INTERP_MPASS, SMOOTH, SPMV, Comm, DeviceHierarchy, DistHierarchy, Hierarchy, NumpyCSR, PartPlan,
     SSS_AMG, SSS_AMG_COMP,
     SSS_AMG_PARS, SSS_HIP_OPTS, SSS_MAT, SSS_RTN, SSS_SMTR, SSS_VEC, coarse_last, csr_arrays, default_pars, device_count,
     hbm_used_bytes, level_step, spmv_enc,
-    generate, interp_exti, interp_std, lib, part_save, pmis, rap_values, read_mtx, std_pattern,
+    agg_graph, generate, interp_exti, interp_mpass, interp_std, lib, part_save, pmis, pmis_agg, rap_values, read_mtx, std_pattern,
 )
 from .workloads import convdiff_csr  # noqa: F401

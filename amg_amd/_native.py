@@ -108,6 +108,8 @@ STEP_NO_PEND = 1
 SMOOTH = {"exact": 0, "hybrid": 1, "jacobi": 2}
 #: SSS_COARSEN_TYPE values of SSS_AMG_PARS.cs_type (3 is an engine extension, the parallel split)
 COARSE_RS, COARSE_PMIS = 1, 3
+#: cs_type 4: aggressive PMIS coarsening on the first SSS_SETUP_AGG_LEVELS levels; interp_type 4: multipass
+COARSE_PMIS_AGG, INTERP_MPASS = 4, 4
 COARSE = {"krylov": 0, "direct": 1}
 VEC = {"b": 0, "x": 1, "wp": 2}
 SPMV = {"mxy": 0, "amxpy": 1, "resid": 2, "acc": 3}
@@ -128,6 +130,8 @@ ABI_SYMBOLS = [
     "sss_hip_setup_create", "sss_amg_setup_hooked", "sss_hip_rap", "sss_hip_pmis", "sss_pmis_host",
     "sss_hip_rap_values", "sss_rap_values_host", "SSS_amg_refresh", "sss_hip_hier_refresh",
     "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std", "sss_hip_interp_exti",
+    "sss_agg_graph_host", "sss_hip_agg_graph", "sss_pmis_agg_host", "sss_interp_mpass_host",
+    "sss_hip_interp_mpass",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
     "SSS_amg_save", "SSS_amg_load",
@@ -217,6 +221,11 @@ def _declare(lib):
         "sss_std_pattern_host": (C.c_int, [P(SSS_IMAT), _int_p, C.c_int, P(SSS_MAT)]),
         "sss_hip_interp_std": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double]),
         "sss_hip_interp_exti": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double]),
+        "sss_agg_graph_host": (C.c_int, [P(SSS_IMAT), _int_p, P(SSS_IMAT)]),
+        "sss_hip_agg_graph": (C.c_int, [P(SSS_IMAT), _int_p, P(SSS_IMAT)]),
+        "sss_pmis_agg_host": (C.c_int, [P(SSS_IMAT), _int_p, _int_p]),
+        "sss_interp_mpass_host": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double, _int_p]),
+        "sss_hip_interp_mpass": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double, _int_p]),
         "SSS_mat_struct_create": (SSS_MAT, [C.c_int, C.c_int, C.c_int]),
         "sss_hip_upload_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_download_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
@@ -424,6 +433,63 @@ def interp_exti(A_csr, S_csr, mark, P_pattern, trunc: float, device: bool = Fals
     result as interp_std; from the host (SSS_amg_interp with interp_type 3) or from the GPU
     (sss_hip_interp_exti).  Raises RuntimeError with the error code (.rc) when the device call fails."""
     return _interp_on_pattern(A_csr, S_csr, mark, P_pattern, trunc, device, 3, "sss_hip_interp_exti", "extended+i")
+
+
+def agg_graph(rp, ci, mark, device: bool = False):
+    """Distance-two graph S2 of the C points of a stage-one split (aggressive coarsening, cs_type
+    COARSE_PMIS_AGG) from a compacted strength matrix and the marks: (row_ptr, col_idx)
+    in C numbering, on the host (sss_agg_graph_host) or on the GPU (sss_hip_agg_graph).  Raises
+    RuntimeError with the error code (.rc) when it fails."""
+    S, keep = _imat(rp, ci)
+    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.int32)
+    S2 = SSS_IMAT()
+    fn = lib().sss_hip_agg_graph if device else lib().sss_agg_graph_host
+    rc = fn(C.byref(S), None if mark is None else iptr(mark), C.byref(S2))
+    if rc != 0:
+        err = RuntimeError(f"aggressive S2 failed ({rc})")
+        err.rc, err.untouched = rc, not S2.row_ptr and S2.num_rows == 0
+        raise err
+    n2 = S2.num_rows
+    rp2 = np.ctypeslib.as_array(S2.row_ptr, shape=(n2 + 1,)).copy()
+    ci2 = np.ctypeslib.as_array(S2.col_idx, shape=(max(int(rp2[n2]), 1),)).copy()[: rp2[n2]]
+    lib().SSS_imat_destroy(C.byref(S2))
+    return rp2, ci2
+
+
+def pmis_agg(rp, ci):
+    """The two-stage split of aggressive coarsening on the host (sss_pmis_agg_host): the PMIS split of
+    S, the PMIS split of S2, the final marks.  Returns (marks, C points)."""
+    S, keep = _imat(rp, ci)
+    mark = np.full(max(S.num_rows, 1), -7, np.int32)
+    nc = C.c_int(-1)
+    rc = lib().sss_pmis_agg_host(C.byref(S), iptr(mark), C.byref(nc))
+    if rc != 0:
+        err = RuntimeError(f"aggressive split failed ({rc})")
+        err.rc = rc
+        raise err
+    return mark[: S.num_rows], nc.value
+
+
+def interp_mpass(A_csr, S_csr, mark, trunc: float, device: bool = False):
+    """Multipass interpolation (interp_type INTERP_MPASS) from A_csr = (row_ptr, col_idx,
+    val), S_csr = (row_ptr, col_idx) and the final marks: pattern and weights pass by pass, the coarse
+    renumbering, the truncation at `trunc`.  Returns (row_ptr, col_idx, val, ncols, passes), from the host
+    (sss_interp_mpass_host) or from the GPU (sss_hip_interp_mpass).  Raises RuntimeError with the error
+    code (.rc) when it fails; P is then untouched (.untouched)."""
+    Am = NumpyCSR(*A_csr)
+    S, keep = _imat(*S_csr)
+    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.int32)
+    P, passes = SSS_MAT(), C.c_int(-1)
+    fn = lib().sss_hip_interp_mpass if device else lib().sss_interp_mpass_host
+    rc = fn(C.byref(Am.mat), C.byref(S), None if mark is None else iptr(mark), C.byref(P), trunc, C.byref(passes))
+    if rc != 0:
+        err = RuntimeError(f"multipass interpolation failed ({rc})")
+        err.rc, err.untouched = rc, not P.row_ptr and P.num_rows == 0
+        raise err
+    try:
+        return (*csr_arrays(P), P.num_cols, passes.value)
+    finally:
+        lib().SSS_mat_destroy(C.byref(P))
 
 
 def _interp_on_pattern(A_csr, S_csr, mark, P_pattern, trunc, device, interp_type, symbol, name):

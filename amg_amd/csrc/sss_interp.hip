@@ -31,7 +31,9 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <climits>
+#include <initializer_list>
 #include <cstring>
 
 namespace sss {
@@ -247,6 +249,488 @@ __global__ __launch_bounds__(kBlock) void pattern_rows(Csr S, const int *__restr
             const int o = prp[i];
             if ((unsigned)o < (unsigned)pnnz) pci[o] = i;
         }
+    }
+}
+
+// ---- the distance-two graph S2 of aggressive coarsening (amg_amd/host/sss_setup.c agg_graph) ----
+// Row c of S2 belongs to C point i = crow[c].  Its candidates, in the host's discovery order: for each
+// k != i of S_i the block (k, then the entries of S_k), of which the C points other than i count.  The
+// first-occurrence rule is the pattern's: claim the column's slot with the sequence number, keep the
+// candidates that own their slot, offsets from an in-order ballot.  Columns are written in C numbering.
+
+// every column of S in range, as the host form checks before it builds anything
+__global__ __launch_bounds__(kBlock) void agg_check_cols(Csr S, int *__restrict__ err)
+{
+    const long long q = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (q < S.nnz && (unsigned)S.ci[q] >= (unsigned)S.n) atomicOr(err, kErrIndex);
+}
+
+// the fine row of every C point, in C numbering (cmap: exclusive sum of the C flags)
+__global__ __launch_bounds__(kBlock) void agg_crow(int n, const int *__restrict__ mark, const int *__restrict__ cmap,
+                                                   int nc, int *__restrict__ crow)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || mark[i] != CGPT) return;
+    const int c = cmap[i];
+    if ((unsigned)c < (unsigned)nc) crow[c] = i;
+}
+
+// candidate bound of every row of S2, the capacity of its global table (0: in LDS), the rows that have one
+__global__ __launch_bounds__(kBlock) void agg_bound(Csr S, const int *__restrict__ crow, int nc, int slots,
+                                                    int *__restrict__ need, long long *__restrict__ gcap,
+                                                    int *__restrict__ ctr)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= nc) return;
+    const int i = crow[c];
+    long long b = 0;
+    if ((unsigned)i >= (unsigned)S.n) {
+        atomicOr(&ctr[0], kErrIndex);
+    } else {
+        int lo, hi;
+        span(S, i, lo, hi);
+        for (int q = lo; q < hi; ++q) {
+            const int k = S.ci[q];
+            if ((unsigned)k >= (unsigned)S.n) {
+                atomicOr(&ctr[0], kErrIndex);
+                continue;
+            }
+            if (k == i) continue;
+            int klo, khi;
+            span(S, k, klo, khi);
+            b += 1 + (khi - klo);
+        }
+    }
+    if (b > kMaxBound) {
+        atomicOr(&ctr[0], kErrBound);
+        b = 0;
+    }
+    need[c] = (int)b;
+    const bool glob = b > slots;
+    gcap[c] = glob ? tab_cap((int)b) : 0;
+    if (glob) atomicAdd(&ctr[1], 1);
+}
+
+// One walk over the candidates of C row i in discovery order; CLAIM and FILL as pattern_walk.
+template <int G, bool CLAIM, bool FILL>
+__device__ __forceinline__ int agg_walk(const Csr &S, const int *__restrict__ mark, const int *__restrict__ cmap, int i,
+                                        int gl, int *key, int *seq, int cap, int *out, int room, int *err)
+{
+    int lo, hi, base = 0, kept = 0;
+    span(S, i, lo, hi);
+    for (int q = lo; q < hi; ++q) {
+        const int k = S.ci[q];
+        if ((unsigned)k >= (unsigned)S.n || k == i) continue;   // out of range: flagged by agg_bound
+        int klo, khi;
+        span(S, k, klo, khi);
+        const int total = 1 + (khi - klo);                      // k itself, then row k of S
+        for (int r0 = 0; r0 < total; r0 += G) {
+            const int r = r0 + gl;
+            int h = -1;
+            if (r < total) {
+                h = r == 0 ? k : S.ci[klo + r - 1];
+                if ((unsigned)h >= (unsigned)S.n) {
+                    atomicOr(err, kErrIndex);
+                    h = -1;
+                } else if (h == i || mark[h] != CGPT) {
+                    h = -1;
+                }
+            }
+            const int s = base + r;
+            if (CLAIM) {
+                if (h >= 0) {
+                    const int slot = tab_insert(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else atomicMin(&seq[slot], s);
+                }
+            } else {
+                bool own = false;
+                if (h >= 0) {
+                    const int slot = tab_find(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else own = seq[slot] == s;
+                }
+                const unsigned long long m = group_ballot<G>(own, gl);
+                if (FILL && own) {
+                    const int o = kept + __popcll(m & ((1ull << gl) - 1ull));
+                    if (o < room) out[o] = cmap[h];
+                }
+                kept += __popcll(m);
+            }
+        }
+        base += total;
+    }
+    return kept;
+}
+
+// count (FILL false: cnt[c]) or fill (s2ci at s2rp[c]) of S2; G lanes per row
+template <int G, bool FILL>
+__global__ __launch_bounds__(kBlock) void agg_rows(Csr S, const int *__restrict__ mark, const int *__restrict__ cmap,
+                                                   const int *__restrict__ crow, int nc, int slots,
+                                                   const int *__restrict__ need, const long long *__restrict__ goff,
+                                                   int *__restrict__ gkey, int *__restrict__ gseq, int *__restrict__ cnt,
+                                                   const int *__restrict__ s2rp, int s2nnz, int *__restrict__ s2ci,
+                                                   int *__restrict__ err)
+{
+    __shared__ int lkey[kLdsSlots], lseq[kLdsSlots];
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    const int c = row < nc ? (int)row : -1;
+    int i = c >= 0 ? crow[c] : -1;
+    if ((unsigned)i >= (unsigned)S.n) i = -1;                   // flagged by agg_bound
+    int *key = nullptr, *seq = nullptr, cap = 0;
+    if (i >= 0) {
+        long long off;
+        cap = row_table(c, grp, slots, need, goff, lkey, gkey, key, off);
+        seq = off >= 0 ? gseq + off : lseq + (-1 - off);
+        for (int s = gl; s < cap; s += G) {
+            key[s] = -1;
+            seq[s] = INT_MAX;
+        }
+    }
+    __syncthreads();
+    if (i >= 0) agg_walk<G, true, false>(S, mark, cmap, i, gl, key, seq, cap, nullptr, 0, err);
+    __syncthreads();
+    if (i >= 0) {
+        int o = 0, room = 0;
+        if (FILL) {
+            o = max(s2rp[c], 0);
+            room = min(s2rp[c + 1], s2nnz) - o;
+        }
+        const int kept = agg_walk<G, false, FILL>(S, mark, cmap, i, gl, key, seq, cap, s2ci + o, room, err);
+        if (FILL) {
+            if (kept != room && gl == 0) atomicOr(err, kErrPatternCol);
+        } else if (gl == 0) {
+            cnt[c] = kept;
+        }
+    } else if (c >= 0 && gl == 0 && !FILL) {
+        cnt[c] = 0;
+    }
+}
+
+// ---- multipass interpolation (amg_amd/host/sss_setup.c mpass_build) ----
+// Pass numbers by relaxation sweeps, then one round of launches per pass over that pass's rows.  The
+// rows of a pass read only the rows of P of the pass before, which sit in that pass's block (pcol,
+// pval; row k at off[k], len[k] entries, fine columns).  The pattern of a row keeps first occurrences
+// in the order of the walk (the stored entries (i, k) of A with k in N_i, row k of P inside); hat w
+// sits in the row's table, a slot owned by lane slot mod G, its terms handed over lane by lane in walk
+// order.  d, tot and sub are computed by every lane of the group.
+
+// consistent input: every index in range, and every strong column k != i of a row in the row of A
+__global__ __launch_bounds__(kBlock) void mpass_check_rows(Csr A, Csr S, int *__restrict__ err)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n) return;
+    int lo, hi, slo, shi;
+    span(A, i, lo, hi);
+    span(S, i, slo, shi);
+    if (A.rp[i] != lo || A.rp[i + 1] != hi || S.rp[i] != slo || S.rp[i + 1] != shi) atomicOr(err, kErrIndex);
+    for (int j = lo; j < hi; ++j)
+        if ((unsigned)A.ci[j] >= (unsigned)A.n) atomicOr(err, kErrIndex);
+    for (int q = slo; q < shi; ++q) {
+        const int k = S.ci[q];
+        if ((unsigned)k >= (unsigned)A.n) {
+            atomicOr(err, kErrIndex);
+            continue;
+        }
+        bool found = k == i;
+        for (int j = lo; j < hi && !found; ++j) found = A.ci[j] == k;
+        if (!found) atomicOr(err, kErrStrongCol);
+    }
+}
+
+// pass 0: a C row is its own column with 1.0, at its coarse number in block 0
+__global__ __launch_bounds__(kBlock) void mpass_init(int n, const int *__restrict__ mark, const int *__restrict__ cmap,
+                                                     int nc, int *__restrict__ pass, int *__restrict__ len,
+                                                     int *__restrict__ off, int *__restrict__ pcol,
+                                                     double *__restrict__ pval)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int c = mark[i] == CGPT ? cmap[i] : -1;
+    const bool coarse = (unsigned)c < (unsigned)nc;
+    pass[i] = coarse ? 0 : -1;
+    len[i] = coarse ? 1 : 0;
+    off[i] = coarse ? c : 0;
+    if (coarse) {
+        pcol[c] = i;
+        pval[c] = 1.0;
+    }
+}
+
+// sweep p: an F point without a number that has a neighbour numbered p - 1 gets p (a reader of pass[]
+// sees -1 or p there, never p - 1); stat[0] counts the points numbered
+__global__ __launch_bounds__(kBlock) void mpass_relax(Csr S, const int *__restrict__ mark, int *pass, int p,
+                                                      unsigned long long *__restrict__ stat)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    bool hit = false;
+    if (i < S.n && mark[i] == FGPT && pass[i] == -1) {
+        int lo, hi;
+        span(S, i, lo, hi);
+        for (int q = lo; q < hi && !hit; ++q) {
+            const int k = S.ci[q];
+            hit = (unsigned)k < (unsigned)S.n && k != i && pass[k] == p - 1;
+        }
+        if (hit) pass[i] = p;
+    }
+    const unsigned long long b = __ballot(hit);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&stat[0], (unsigned long long)__popcll(b));
+}
+
+__global__ __launch_bounds__(kBlock) void mpass_select(int n, const int *__restrict__ pass, int p, int *__restrict__ flag)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i <= n) flag[i] = i < n && pass[i] == p;
+}
+
+__global__ __launch_bounds__(kBlock) void mpass_scatter(int n, const int *__restrict__ pass, int p,
+                                                        const int *__restrict__ pos, int cnt, int *__restrict__ rows)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n && pass[i] == p && (unsigned)pos[i] < (unsigned)cnt) rows[pos[i]] = i;
+}
+
+// whether the stored entry (i, k) of A has k in N_i: k != i, in S_i, of the pass before
+__device__ __forceinline__ bool mpass_in_n(const Csr &S, int slo, int shi, const int *__restrict__ pass, int i, int k,
+                                           int p)
+{
+    if (k == i || pass[k] != p - 1) return false;
+    for (int q = slo; q < shi; ++q)
+        if (S.ci[q] == k) return true;
+    return false;
+}
+
+// the block of the pass before: row k of P at off[k], len[k] entries (checked against the block)
+struct PrevBlock {
+    const int *len, *off, *col;
+    const double *val;
+    int nnz;
+};
+__device__ __forceinline__ bool prev_row(const PrevBlock &B, int k, int &o, int &l, int *err)
+{
+    o = B.off[k], l = B.len[k];
+    if (o < 0 || l < 0 || (long long)o + l > B.nnz) {
+        atomicOr(err, kErrIndex);
+        return false;
+    }
+    return true;
+}
+
+// candidate bound of the rows of a pass (the rows of P of N_i, one after the other); stat[1] their sum
+__global__ __launch_bounds__(kBlock) void mpass_bound(Csr A, Csr S, const int *__restrict__ pass, PrevBlock B,
+                                                      const int *__restrict__ rows, int cnt, int p, int *__restrict__ need,
+                                                      unsigned long long *__restrict__ stat, int *__restrict__ ctr)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    long long b = 0;
+    if (t < cnt) {
+        const int i = rows[t];
+        int lo, hi, slo, shi;
+        span(A, i, lo, hi);
+        span(S, i, slo, shi);
+        for (int j = lo; j < hi; ++j) {
+            const int k = A.ci[j];
+            if ((unsigned)k >= (unsigned)A.n) continue;   // flagged by mpass_check_rows
+            int o, l;
+            if (mpass_in_n(S, slo, shi, pass, i, k, p) && prev_row(B, k, o, l, &ctr[0])) b += l;
+        }
+        if (b > kMaxBound) {
+            atomicOr(&ctr[0], kErrBound);
+            b = 0;
+        }
+        need[t] = (int)b;
+    }
+    unsigned long long sum = (unsigned long long)b;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&stat[1], sum);
+}
+
+// the capacity of every row's global table (0: in LDS) and the rows that have one
+__global__ __launch_bounds__(kBlock) void mpass_gcap(int cnt, int slots, const int *__restrict__ need,
+                                                     long long *__restrict__ gcap, int *__restrict__ ctr)
+{
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    if (t > cnt) return;
+    const bool glob = t < cnt && need[t] > slots;
+    gcap[t] = glob ? tab_cap(need[t]) : 0;
+    if (glob) atomicAdd(&ctr[1], 1);
+}
+
+// One walk over the candidates of row i of pass p in discovery order; CLAIM and FILL as pattern_walk.
+template <int G, bool CLAIM, bool FILL>
+__device__ __forceinline__ int mpass_walk(const Csr &A, const Csr &S, const int *__restrict__ pass, const PrevBlock &B, int i,
+                                          int p, int gl, int *key, int *seq, int cap, int *out, int room, int *err)
+{
+    int lo, hi, slo, shi, base = 0, kept = 0;
+    span(A, i, lo, hi);
+    span(S, i, slo, shi);
+    for (int j = lo; j < hi; ++j) {
+        const int k = A.ci[j];
+        int ko, kl;
+        if ((unsigned)k >= (unsigned)A.n || !mpass_in_n(S, slo, shi, pass, i, k, p) || !prev_row(B, k, ko, kl, err)) continue;
+        for (int r0 = 0; r0 < kl; r0 += G) {
+            const int r = r0 + gl;
+            int h = -1;
+            if (r < kl) {
+                h = B.col[ko + r];
+                if ((unsigned)h >= (unsigned)A.n) {
+                    atomicOr(err, kErrIndex);
+                    h = -1;
+                }
+            }
+            const int s = base + r;
+            if (CLAIM) {
+                if (h >= 0) {
+                    const int slot = tab_insert(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else atomicMin(&seq[slot], s);
+                }
+            } else {
+                bool own = false;
+                if (h >= 0) {
+                    const int slot = tab_find(key, cap, h);
+                    if (slot < 0) atomicOr(err, kErrTableFull);
+                    else own = seq[slot] == s;
+                }
+                const unsigned long long m = group_ballot<G>(own, gl);
+                if (FILL && own) {
+                    const int o = kept + __popcll(m & ((1ull << gl) - 1ull));
+                    if (o < room) out[o] = h;
+                }
+                kept += __popcll(m);
+            }
+        }
+        base += kl;
+    }
+    return kept;
+}
+
+// The rows of pass p, G lanes per row.  FILL false: the pattern lengths into cnt[t].  FILL true: the
+// pattern and the weights into the pass's block at boff[t], and the row's len and off for the next pass.
+template <int G, bool FILL>
+__global__ __launch_bounds__(kBlock) void mpass_rows(Csr A, Csr S, const int *__restrict__ pass, PrevBlock B,
+                                                     const int *__restrict__ rows, int nrows, int p, int slots,
+                                                     const int *__restrict__ need, const long long *__restrict__ goff,
+                                                     int *__restrict__ gkey, int *__restrict__ gseq, double *__restrict__ gacc,
+                                                     int *__restrict__ cnt, const int *__restrict__ boff, int bnnz,
+                                                     int *__restrict__ bcol, double *__restrict__ bval, int *len, int *off,
+                                                     int *__restrict__ err)
+{
+    __shared__ int lkey[kLdsSlots], lseq[kLdsSlots];
+    __shared__ double lacc[FILL ? kLdsSlots : 1];
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    const int t = row < nrows ? (int)row : -1;
+    int i = t >= 0 ? rows[t] : -1;
+    if ((unsigned)i >= (unsigned)A.n) i = -1;
+    int *key = nullptr, *seq = nullptr, cap = 0;
+    double *acc = nullptr;
+    if (i >= 0) {
+        long long toff;
+        cap = row_table(t, grp, slots, need, goff, lkey, gkey, key, toff);
+        seq = toff >= 0 ? gseq + toff : lseq + (-1 - toff);
+        if (FILL) acc = toff >= 0 ? gacc + toff : lacc + (-1 - toff);
+        for (int s = gl; s < cap; s += G) {
+            key[s] = -1;
+            seq[s] = INT_MAX;
+            if (FILL) acc[s] = 0.0;
+        }
+    }
+    __syncthreads();
+    if (i >= 0) mpass_walk<G, true, false>(A, S, pass, B, i, p, gl, key, seq, cap, nullptr, 0, err);
+    __syncthreads();
+    int o = 0, room = 0;
+    if (i >= 0) {
+        if (FILL) {
+            o = max(boff[t], 0);
+            room = max(min(boff[t + 1], bnnz) - o, 0);
+        }
+        const int kept = mpass_walk<G, false, FILL>(A, S, pass, B, i, p, gl, key, seq, cap, bcol + o, room, err);
+        if (FILL) {
+            if (kept != room && gl == 0) atomicOr(err, kErrPatternCol);
+        } else if (gl == 0) {
+            cnt[t] = kept;
+        }
+    }
+    if (!FILL) return;
+    __syncthreads();
+    double d = 0.0, tot = 0.0, sub = 0.0;
+    if (i >= 0) {
+        int lo, hi, slo, shi;
+        span(A, i, lo, hi);
+        span(S, i, slo, shi);
+        for (int j = lo; j < hi; ++j) {
+            const int k = A.ci[j];
+            if ((unsigned)k >= (unsigned)A.n) continue;   // flagged by mpass_check_rows
+            const double a = A.v[j];
+            if (k == i) {
+                d = a;
+                continue;
+            }
+            tot += a;
+            int ko, kl;
+            if (!mpass_in_n(S, slo, shi, pass, i, k, p)) continue;
+            sub += a;
+            if (!prev_row(B, k, ko, kl, err)) continue;
+            for (int r0 = 0; r0 < kl; r0 += G) {
+                const int r = r0 + gl;
+                int slot = -1;
+                double prod = 0.0;
+                if (r < kl) {
+                    const int c = B.col[ko + r];
+                    if ((unsigned)c < (unsigned)A.n) {
+                        slot = tab_find(key, cap, c);
+                        if (slot < 0) atomicOr(err, kErrPatternCol);
+                        prod = a * B.val[ko + r];
+                    }
+                }
+                // handed to the owners in walk order: lane u's term is applied before lane u + 1's
+                const int nl = min(G, kl - r0);
+                for (int u = 0; u < nl; ++u) {
+                    const int su = __shfl(slot, u, G);
+                    const double vu = __shfl(prod, u, G);
+                    if (su >= 0 && (su & (G - 1)) == gl) acc[su] += vu;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (i >= 0) {
+        const bool zero = sub == 0.0 || d == 0.0;
+        const double f = zero ? 0.0 : tot / sub;
+        for (int q = gl; q < room; q += G) {
+            const int c = bcol[o + q];
+            const int slot = (unsigned)c < (unsigned)A.n ? tab_find(key, cap, c) : -1;
+            if (slot >= 0) bval[o + q] = zero ? 0.0 : -(f * acc[slot]) / d;
+        }
+        if (gl == 0) {
+            len[i] = room;
+            off[i] = o;
+        }
+    }
+}
+
+// P in row order (fine columns) from the blocks: row i of pass q is in block q at off[i]
+__global__ __launch_bounds__(kBlock) void mpass_assemble(int n, const int *__restrict__ pass, const int *__restrict__ len,
+                                                         const int *__restrict__ off, int nblocks,
+                                                         const int *const *__restrict__ bcol,
+                                                         const double *const *__restrict__ bval,
+                                                         const int *__restrict__ bnnz, const int *__restrict__ prp, int pnnz,
+                                                         int *__restrict__ pci, double *__restrict__ pv, int *__restrict__ err)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int l = len[i], b = pass[i];
+    if (l <= 0) return;
+    const int o = off[i], w = prp[i];
+    if ((unsigned)b >= (unsigned)nblocks || o < 0 || (long long)o + l > bnnz[b] || w < 0 || (long long)w + l > pnnz) {
+        atomicOr(err, kErrIndex);
+        return;
+    }
+    for (int q = 0; q < l; ++q) {
+        pci[w + q] = bcol[b][o + q];
+        pv[w + q] = bval[b][o + q];
     }
 }
 
@@ -665,15 +1149,19 @@ int copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind k, hipStre
 
 // lanes per row from the average row of S: an F row has about avg + avg^2 / 2 candidates, and a group
 // of G lanes has 8 G table slots in LDS (SSS_HIP_INTERP_LANES, tests: 1, 4, 16 or 64 whatever the rows)
-int lanes_for(int n, int snnz)
+int lanes_for_candidates(double est)
 {
     const char *e = getenv("SSS_HIP_INTERP_LANES");
     if (e && *e) {
         const int g = atoi(e);
         if (g == 1 || g == 4 || g == 16 || g == 64) return g;
     }
-    const double avg = (double)snnz / (double)std::max(n, 1), est = avg * (1.0 + 0.5 * avg);
     return est <= 4.0 ? 1 : est <= 16.0 ? 4 : est <= 64.0 ? 16 : 64;
+}
+int lanes_for(int n, int snnz)
+{
+    const double avg = (double)snnz / (double)std::max(n, 1);
+    return lanes_for_candidates(avg * (1.0 + 0.5 * avg));
 }
 
 // table slots of one group in LDS, a power of two (SSS_HIP_INTERP_LDS_SLOTS lowers it: the tests
@@ -713,6 +1201,17 @@ struct Dev {
         T *p = alloc<T>(count);
         if (p && count && h2d(p, src, sizeof(T) * count)) oom = true;
         return p;
+    }
+    // frees what was allocated since mem held `from` arrays, but for the arrays of `keep`
+    void free_from(size_t from, std::initializer_list<void *> keep)
+    {
+        std::vector<void *> kept;
+        for (size_t q = from; q < mem.size(); ++q) {
+            if (std::find(keep.begin(), keep.end(), mem[q]) != keep.end()) kept.push_back(mem[q]);
+            else dev_free(mem[q]);
+        }
+        mem.resize(from);
+        mem.insert(mem.end(), kept.begin(), kept.end());
     }
     // the time since the last call goes to the copies or to the kernels
     void lap(bool copy)
@@ -849,7 +1348,91 @@ static void launch_exti(int G, hipStream_t st, int n, Args... a)
 {
     SSS_INTERP_LAUNCH(exti_rows)
 }
+template <bool FILL, class... Args>
+static void launch_agg(int G, hipStream_t st, int n, Args... a)
+{
+    SSS_INTERP_LAUNCH(agg_rows, FILL)
+}
 #undef SSS_INTERP_LAUNCH
+
+extern "C" int sss_hip_agg_graph(const SSS_IMAT *S, const int *mark, SSS_IMAT *S2)
+{
+    const char *what = "aggressive S2";
+    if (!S2) return ERROR_INPUT_PAR;
+    if (int rc = check_s(S, mark)) return rc;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    const int n = S->num_rows, nnz = S->row_ptr[n];
+    Dev d;
+    if (hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+    Tables t;
+    t.S.n = n, t.S.nnz = nnz, t.S.v = nullptr;
+    t.S.rp = d.upload(S->row_ptr, (size_t)n + 1);
+    t.S.ci = d.upload(S->col_idx, (size_t)nnz);
+    t.mark = d.upload(mark, (size_t)n);
+    t.ctr = d.alloc<int>(2);
+    int *flag = d.alloc<int>((size_t)n + 1), *cmap = d.alloc<int>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(aggressive S2)", __FILE__, __LINE__);
+    d.lap(true);
+    // the C numbering and the fine row of every C point
+    int nc = 0, h_ctr[2];
+    SSS_HIP(hipMemsetAsync(t.ctr, 0, sizeof(int) * 2, d.st));
+    if (nnz > 0) hipLaunchKernelGGL(agg_check_cols, dim3(grid_for(nnz)), dim3(kBlock), 0, d.st, t.S, t.ctr);
+    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
+    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    if (copy_sync(&nc, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (nc < 0 || nc > n) return ERROR_MISC;
+    int *crow = d.alloc<int>((size_t)nc), *cnt = d.alloc<int>((size_t)nc + 1), *s2rp = d.alloc<int>((size_t)nc + 1);
+    long long *gcap = d.alloc<long long>((size_t)nc + 1);
+    t.need = d.alloc<int>((size_t)nc);
+    t.goff = d.alloc<long long>((size_t)nc + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(aggressive S2)", __FILE__, __LINE__);
+    // every k of a row is an intermediate point: about avg (1 + avg) candidates
+    const double avg = (double)nnz / (double)n;
+    t.G = lanes_for_candidates(avg * (1.0 + avg));
+    t.slots = slots_for(t.G);
+    int *s2ci = nullptr, s2nnz = 0;
+    if (nc > 0) {
+        hipLaunchKernelGGL(agg_crow, dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, t.mark, cmap, nc, crow);
+        SSS_HIP(hipMemsetAsync(gcap + nc, 0, sizeof(long long), d.st));
+        hipLaunchKernelGGL(agg_bound, dim3(grid_for(nc)), dim3(kBlock), 0, d.st, t.S, crow, nc, t.slots, t.need, gcap, t.ctr);
+        if (int rc = exclusive_sum(d, gcap, t.goff, (size_t)nc + 1)) return rc;
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        if (copy_sync(&t.total, t.goff + nc, sizeof(long long), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+        t.global_rows = h_ctr[1];
+        t.gkey = d.alloc<int>((size_t)t.total);
+        int *gseq = d.alloc<int>((size_t)t.total);
+        if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(global tables)", __FILE__, __LINE__);
+        SSS_HIP(hipMemsetAsync(cnt + nc, 0, sizeof(int), d.st));
+        launch_agg<false>(t.G, d.st, nc, t.S, t.mark, cmap, crow, nc, t.slots, t.need, t.goff, t.gkey, gseq, cnt, s2rp, s2nnz,
+                          s2ci, t.ctr);
+        if (int rc = exclusive_sum(d, cnt, s2rp, (size_t)nc + 1)) return rc;
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        if (copy_sync(&s2nnz, s2rp + nc, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+        if (s2nnz < 0) return ERROR_MAT_SIZE;
+        s2ci = d.alloc<int>((size_t)s2nnz);
+        if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(aggressive S2)", __FILE__, __LINE__);
+        launch_agg<true>(t.G, d.st, nc, t.S, t.mark, cmap, crow, nc, t.slots, t.need, t.goff, t.gkey, gseq, cnt, s2rp, s2nnz,
+                         s2ci, t.ctr);
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    }
+    d.lap(false);
+
+    // into arrays of its own first: S2 stays untouched if a copy fails
+    HostArr<int> rp((size_t)nc + 1), ci((size_t)s2nnz);
+    if (nc > 0 && copy_sync(rp.p, s2rp, sizeof(int) * ((size_t)nc + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(ci.p, s2ci, sizeof(int) * (size_t)s2nnz, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    d.lap(true);
+    memset(S2, 0, sizeof(*S2));
+    S2->num_rows = S2->num_cols = nc;
+    S2->num_nnzs = s2nnz;
+    S2->row_ptr = rp.release();
+    S2->col_idx = ci.release();
+    if (getenv("SSS_SETUP_TIMING"))
+        fprintf(stderr, "[setup]   aggressive S2: device, %d rows, %d entries, %d lanes per row, %d rows on global tables, "
+                        "copies %.4f s, kernels %.4f s\n", nc, s2nnz, t.G, t.global_rows, d.t_copy, d.t_kern);
+    return 0;
+}
 
 extern "C" int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P)
 {
@@ -893,6 +1476,211 @@ extern "C" int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoar
     return 0;
 }
 
+// The tail of every interpolation: the coarse numbers of the columns of (prp, pci, pv), the truncation,
+// the download.  P is written after the last copy only; `replace` frees the arrays it held.
+static int renumber_truncate(Dev &d, const Tables &t, const char *what, int n, const int *prp, int *pci, const double *pv,
+                             int pnnz, double trunc_threshold, SSS_MAT *P, bool replace)
+{
+    int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
+    int *cnt = d.alloc<int>((size_t)n + 1), *nrp = d.alloc<int>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
+    SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
+    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
+    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
+    if (pnnz > 0) hipLaunchKernelGGL(renumber, dim3(grid_for(pnnz)), dim3(kBlock), 0, d.st, pnnz, n, cmap, pci, t.ctr);
+    hipLaunchKernelGGL((trunc_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
+                       nrp, 0, nullptr, nullptr);
+    if (int rc = exclusive_sum(d, cnt, nrp, (size_t)n + 1)) return rc;
+    int h_ctr[2], kept = 0, ncoarse = 0;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    if (copy_sync(&kept, nrp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (kept < 0 || kept > pnnz) return ERROR_MAT_SIZE;
+    int *nci = d.alloc<int>((size_t)kept);
+    double *nv = d.alloc<double>((size_t)kept);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
+    hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
+                       nrp, kept, nci, nv);
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    d.lap(false);
+
+    // into arrays of its own first: P stays untouched if a copy fails
+    HostArr<int> rp((size_t)n + 1), ci((size_t)kept);
+    HostArr<double> val((size_t)kept);
+    if (copy_sync(rp.p, nrp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(ci.p, nci, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    if (copy_sync(val.p, nv, sizeof(double) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    d.lap(true);
+    if (replace) {
+        free(P->row_ptr);
+        free(P->col_idx);
+        free(P->val);
+    } else {
+        memset(P, 0, sizeof(*P));
+        P->num_rows = n;
+    }
+    P->num_cols = ncoarse;
+    P->num_nnzs = kept;
+    P->row_ptr = rp.release();
+    P->col_idx = ci.release();
+    P->val = val.release();
+    return 0;
+}
+
+template <bool FILL, class... Args>
+static void launch_mpass(int G, hipStream_t st, int n, Args... a)
+{
+    switch (G) {
+    case 1: hipLaunchKernelGGL((mpass_rows<1, FILL>), dim3(grid_for(n)), dim3(kBlock), 0, st, a...); break;
+    case 4: hipLaunchKernelGGL((mpass_rows<4, FILL>), dim3(grid_for(4LL * n)), dim3(kBlock), 0, st, a...); break;
+    case 16: hipLaunchKernelGGL((mpass_rows<16, FILL>), dim3(grid_for(16LL * n)), dim3(kBlock), 0, st, a...); break;
+    default: hipLaunchKernelGGL((mpass_rows<64, FILL>), dim3(grid_for(64LL * n)), dim3(kBlock), 0, st, a...); break;
+    }
+}
+
+extern "C" int sss_hip_interp_mpass(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold,
+                                    int *passes)
+{
+    const char *what = "multipass interpolation";
+    if (!A || !P || !A->row_ptr) return ERROR_INPUT_PAR;
+    if (int rc = check_s(S, mark)) return rc;
+    const int n = S->num_rows, snnz = S->row_ptr[n];
+    if (A->num_rows != n || A->row_ptr[0] != 0) return ERROR_INPUT_PAR;
+    const int annz = A->row_ptr[n];
+    if (annz <= 0 || !A->col_idx || !A->val) return ERROR_INPUT_PAR;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    Dev d;
+    if (hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+    hipStream_t st = d.st;
+    Tables t;
+    t.S.n = n, t.S.nnz = snnz, t.S.v = nullptr;
+    t.S.rp = d.upload(S->row_ptr, (size_t)n + 1);
+    t.S.ci = d.upload(S->col_idx, (size_t)snnz);
+    t.mark = d.upload(mark, (size_t)n);
+    Csr Ad{n, annz, nullptr, nullptr, nullptr};
+    Ad.rp = d.upload(A->row_ptr, (size_t)n + 1);
+    Ad.ci = d.upload(A->col_idx, (size_t)annz);
+    Ad.v = d.upload(A->val, (size_t)annz);
+    t.ctr = d.alloc<int>(2);
+    unsigned long long *stat = d.alloc<unsigned long long>(2), h_stat[2] = {0, 0};
+    int *flag = d.alloc<int>((size_t)n + 1), *pos = d.alloc<int>((size_t)n + 1);
+    int *pass = d.alloc<int>((size_t)n), *len = d.alloc<int>((size_t)n), *off = d.alloc<int>((size_t)n);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(multipass interpolation)", __FILE__, __LINE__);
+    d.lap(true);
+
+    // consistency, the coarse numbers, pass 0 (block 0: the C rows)
+    int h_ctr[2], nc = 0;
+    SSS_HIP(hipMemsetAsync(t.ctr, 0, sizeof(int) * 2, st));
+    hipLaunchKernelGGL(mpass_check_rows, dim3(grid_for(n)), dim3(kBlock), 0, st, Ad, t.S, t.ctr);
+    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, st, n, t.mark, flag);
+    if (int rc = exclusive_sum(d, flag, pos, (size_t)n + 1)) return rc;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    if (copy_sync(&nc, pos + n, sizeof(int), hipMemcpyDeviceToHost, st)) return ERROR_MISC;
+    if (nc < 0 || nc > n) return ERROR_MISC;
+    std::vector<int *> bcol{d.alloc<int>((size_t)nc)};
+    std::vector<double *> bval{d.alloc<double>((size_t)nc)};
+    std::vector<int> bnnz{nc};
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(multipass interpolation)", __FILE__, __LINE__);
+    hipLaunchKernelGGL(mpass_init, dim3(grid_for(n)), dim3(kBlock), 0, st, n, t.mark, pos, nc, pass, len, off, bcol[0], bval[0]);
+
+    // pass numbers: sweeps until one numbers nobody (at most n of them number somebody)
+    std::vector<int> rows_of{nc};
+    long long numbered = nc;
+    for (int p = 1; p <= n; ++p) {
+        SSS_HIP(hipMemsetAsync(stat, 0, sizeof(unsigned long long) * 2, st));
+        hipLaunchKernelGGL(mpass_relax, dim3(grid_for(n)), dim3(kBlock), 0, st, t.S, t.mark, pass, p, stat);
+        SSS_HIP(hipGetLastError());
+        if (copy_sync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st)) return ERROR_MISC;
+        if (h_stat[0] == 0) break;
+        if (h_stat[0] > (unsigned long long)n) return ERROR_MISC;
+        rows_of.push_back((int)h_stat[0]);
+        numbered += (long long)h_stat[0];
+    }
+    const int npass = (int)rows_of.size() - 1;
+
+    // one round of launches per pass, over that pass's rows
+    long long total_nnz = nc;
+    int max_lanes = 1;
+    for (int p = 1; p <= npass; ++p) {
+        const size_t scope = d.mem.size();
+        const int cnt = rows_of[p];
+        int *rows = d.alloc<int>((size_t)cnt), *rcnt = d.alloc<int>((size_t)cnt + 1), *boff = d.alloc<int>((size_t)cnt + 1);
+        long long *gcap = d.alloc<long long>((size_t)cnt + 1);
+        t.need = d.alloc<int>((size_t)cnt);
+        t.goff = d.alloc<long long>((size_t)cnt + 1);
+        if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(multipass interpolation)", __FILE__, __LINE__);
+        hipLaunchKernelGGL(mpass_select, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, st, n, pass, p, flag);
+        if (int rc = exclusive_sum(d, flag, pos, (size_t)n + 1)) return rc;
+        hipLaunchKernelGGL(mpass_scatter, dim3(grid_for(n)), dim3(kBlock), 0, st, n, pass, p, pos, cnt, rows);
+        const PrevBlock B{len, off, bcol[p - 1], bval[p - 1], bnnz[p - 1]};
+        SSS_HIP(hipMemsetAsync(stat, 0, sizeof(unsigned long long) * 2, st));
+        hipLaunchKernelGGL(mpass_bound, dim3(grid_for(cnt)), dim3(kBlock), 0, st, Ad, t.S, pass, B, rows, cnt, p, t.need, stat,
+                           t.ctr);
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        if (copy_sync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, st)) return ERROR_MISC;
+        // the bound is at least the pass's entries: the device gives up where they might not fit an int
+        if (total_nnz + (long long)h_stat[1] > INT_MAX) return ERROR_MAT_SIZE;
+        // G from the pass's average candidate bound
+        t.G = lanes_for_candidates((double)h_stat[1] / (double)cnt);
+        t.slots = slots_for(t.G);
+        max_lanes = std::max(max_lanes, t.G);
+        hipLaunchKernelGGL(mpass_gcap, dim3(grid_for((long long)cnt + 1)), dim3(kBlock), 0, st, cnt, t.slots, t.need, gcap, t.ctr);
+        if (int rc = exclusive_sum(d, gcap, t.goff, (size_t)cnt + 1)) return rc;
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        if (copy_sync(&t.total, t.goff + cnt, sizeof(long long), hipMemcpyDeviceToHost, st)) return ERROR_MISC;
+        t.global_rows = h_ctr[1];
+        t.gkey = d.alloc<int>((size_t)t.total);
+        int *gseq = d.alloc<int>((size_t)t.total);
+        double *gacc = d.alloc<double>((size_t)t.total);
+        if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(global tables)", __FILE__, __LINE__);
+        SSS_HIP(hipMemsetAsync(rcnt + cnt, 0, sizeof(int), st));
+        launch_mpass<false>(t.G, st, cnt, Ad, t.S, (const int *)pass, B, (const int *)rows, cnt, p, t.slots, (const int *)t.need,
+                            (const long long *)t.goff, t.gkey, gseq, gacc, rcnt, (const int *)boff, 0, (int *)nullptr,
+                            (double *)nullptr, len, off, t.ctr);
+        if (int rc = exclusive_sum(d, rcnt, boff, (size_t)cnt + 1)) return rc;
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        int nnz_p = 0;
+        if (copy_sync(&nnz_p, boff + cnt, sizeof(int), hipMemcpyDeviceToHost, st)) return ERROR_MISC;
+        if (nnz_p < 0 || (unsigned long long)nnz_p > h_stat[1]) return ERROR_MISC;
+        bcol.push_back(d.alloc<int>((size_t)nnz_p));
+        bval.push_back(d.alloc<double>((size_t)nnz_p));
+        bnnz.push_back(nnz_p);
+        if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(multipass interpolation)", __FILE__, __LINE__);
+        launch_mpass<true>(t.G, st, cnt, Ad, t.S, (const int *)pass, B, (const int *)rows, cnt, p, t.slots, (const int *)t.need,
+                           (const long long *)t.goff, t.gkey, gseq, gacc, rcnt, (const int *)boff, nnz_p, bcol[p], bval[p], len, off,
+                           t.ctr);
+        if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+        total_nnz += nnz_p;
+        // the pass's scratch goes, its block stays
+        d.free_from(scope, {bcol[p], bval[p]});
+        t.need = nullptr, t.goff = nullptr, t.gkey = nullptr;
+    }
+    const int global_rows_all = h_ctr[1];   // ctr[1] is never reset: the rows on global tables of all passes
+
+    // P in row order, fine columns
+    const int pnnz = (int)total_nnz;
+    int *prp = d.alloc<int>((size_t)n + 1), *pci = d.alloc<int>((size_t)pnnz), *d_bnnz = d.upload(bnnz.data(), bnnz.size());
+    double *pv = d.alloc<double>((size_t)pnnz);
+    int **d_bcol = d.upload(bcol.data(), bcol.size());
+    double **d_bval = d.upload(bval.data(), bval.size());
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(multipass interpolation)", __FILE__, __LINE__);
+    SSS_HIP(hipMemcpyAsync(flag, len, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    SSS_HIP(hipMemsetAsync(flag + n, 0, sizeof(int), st));
+    if (int rc = exclusive_sum(d, flag, prp, (size_t)n + 1)) return rc;
+    hipLaunchKernelGGL(mpass_assemble, dim3(grid_for(n)), dim3(kBlock), 0, st, n, pass, len, off, (int)bcol.size(), d_bcol, d_bval,
+                       d_bnnz, prp, pnnz, pci, pv, t.ctr);
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    t.G = max_lanes;
+    t.global_rows = global_rows_all;
+    if (int rc = renumber_truncate(d, t, what, n, prp, pci, pv, pnnz, trunc_threshold, P, false)) return rc;
+    if (passes) *passes = npass;
+    if (getenv("SSS_SETUP_TIMING"))
+        fprintf(stderr, "[setup]   multipass P: device, %d passes, %lld rows unreached, %d rows, %d entries, up to %d lanes per row, "
+                        "%d rows on global tables, copies %.4f s, kernels %.4f s\n", npass, (long long)n - numbered, n, P->num_nnzs,
+                max_lanes, global_rows_all, d.t_copy, d.t_kern);
+    return 0;
+}
+
 // the weights of interp_STD or (exti) interp_EXTI on a pattern, the coarse renumbering, the truncation
 static int interp_weights(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold, bool exti)
 {
@@ -919,11 +1707,8 @@ static int interp_weights(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, 
     double *gacc = d.alloc<double>((size_t)t.total), *pv = d.alloc<double>((size_t)pnnz);
     double *diag = d.alloc<double>((size_t)n), *csum = nullptr, *nsum = nullptr, *psum = nullptr;
     if (!exti) csum = d.alloc<double>((size_t)n), nsum = d.alloc<double>((size_t)n), psum = d.alloc<double>((size_t)n);
-    int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
-    int *cnt = d.alloc<int>((size_t)n + 1), *nrp = d.alloc<int>((size_t)n + 1);
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
     SSS_HIP(hipMemsetAsync(pv, 0, sizeof(double) * (size_t)std::max(pnnz, 1), d.st));
-    SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
     if (exti) {
         hipLaunchKernelGGL(exti_diag, dim3(grid_for(n)), dim3(kBlock), 0, d.st, Ad, diag);
         launch_exti(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
@@ -933,42 +1718,8 @@ static int interp_weights(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, 
         launch_weights(t.G, d.st, n, Ad, t.S, t.mark, t.slots, t.need, t.goff, t.gkey, gacc, prp, pnnz, (const int *)pci, pv,
                        (const double *)diag, (const double *)csum, (const double *)nsum, (const double *)psum, t.ctr);
     }
-    // the coarse numbers of the columns, then the truncation
-    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
-    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
-    if (pnnz > 0) hipLaunchKernelGGL(renumber, dim3(grid_for(pnnz)), dim3(kBlock), 0, d.st, pnnz, n, cmap, pci, t.ctr);
-    hipLaunchKernelGGL((trunc_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
-                       nrp, 0, nullptr, nullptr);
-    if (int rc = exclusive_sum(d, cnt, nrp, (size_t)n + 1)) return rc;
-    int h_ctr[2], kept = 0, ncoarse = 0;
-    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
-    if (copy_sync(&kept, nrp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    if (kept < 0 || kept > pnnz) return ERROR_MAT_SIZE;
-    int *nci = d.alloc<int>((size_t)kept);
-    double *nv = d.alloc<double>((size_t)kept);
-    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(standard weights)", __FILE__, __LINE__);
-    hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
-                       nrp, kept, nci, nv);
-    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
-    d.lap(false);
-
-    // into arrays of its own first: P stays untouched if a copy fails
-    HostArr<int> rp((size_t)n + 1), ci((size_t)kept);
-    HostArr<double> val((size_t)kept);
-    if (copy_sync(rp.p, nrp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    if (copy_sync(ci.p, nci, sizeof(int) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    if (copy_sync(val.p, nv, sizeof(double) * (size_t)kept, hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    d.lap(true);
-    free(P->row_ptr);
-    free(P->col_idx);
-    free(P->val);
-    P->num_cols = ncoarse;
-    P->num_nnzs = kept;
-    P->row_ptr = rp.release();
-    P->col_idx = ci.release();
-    P->val = val.release();
-    timing_line("weights", d, t, n, kept, exti ? "extended+i" : "standard");
+    if (int rc = renumber_truncate(d, t, what, n, prp, pci, pv, pnnz, trunc_threshold, P, true)) return rc;
+    timing_line("weights", d, t, n, P->num_nnzs, exti ? "extended+i" : "standard");
     return 0;
 }
 

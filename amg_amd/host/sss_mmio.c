@@ -345,9 +345,17 @@ void SSS_amg_pars_init(SSS_AMG_PARS *pars)
         pars->cs_type = SSS_COARSE_PMIS;
         pars->interp_type = intERP_STD;
     }
-    /* SSS_SETUP_INTERP=exti, read after the split's choice: the extended+i weights on the same pattern */
+    /* SSS_SETUP_COARSEN=pmis-agg: aggressive coarsening on the first SSS_SETUP_AGG_LEVELS levels (with
+     * multipass interpolation there), the parallel split and its partner below them */
+    if (cs && strcmp(cs, "pmis-agg") == 0) {
+        pars->cs_type = SSS_COARSE_PMIS_AGG;
+        pars->interp_type = intERP_STD;
+    }
+    /* SSS_SETUP_INTERP=exti, read after the split's choice: the extended+i weights on the same pattern;
+     * SSS_SETUP_INTERP=mpass: multipass interpolation on every level */
     const char *it = getenv("SSS_SETUP_INTERP");
     if (it && strcmp(it, "exti") == 0) pars->interp_type = intERP_EXTI;
+    if (it && strcmp(it, "mpass") == 0) pars->interp_type = intERP_MPASS;
 }
 
 /* SSS_main.c:67-119 — byte-identical stdout. */
@@ -377,6 +385,8 @@ void SSS_amg_pars_print(SSS_AMG_PARS *pars)
         printf("AMG interPolation type:            STD\n");
     else if (pars->interp_type == intERP_EXTI)
         printf("AMG interPolation type:            EXTI\n");
+    else if (pars->interp_type == intERP_MPASS)
+        printf("AMG interPolation type:            MPASS\n");
     printf("AMG dof on coarsest grid:          %d\n", pars->coarse_dof);
     printf("AMG strong threshold:              %.4lf\n", pars->strong_threshold);
     printf("AMG truncation threshold:          %.4lf\n", pars->trunc_threshold);

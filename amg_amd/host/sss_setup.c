@@ -33,6 +33,7 @@
  */
 #include "sss_internal.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -762,6 +763,180 @@ int sss_std_pattern_host(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MA
     return 0;
 }
 
+/* ======================================================================================
+ * Aggressive coarsening (cs_type SSS_COARSE_PMIS_AGG; an engine extension): the PMIS
+ * split, then a second PMIS split over the distance-two graph S2 of its C points.
+ *
+ * S2 has one row per stage-one C point, numbered c(i) in increasing i.  Row c(i) is one walk of S_i in
+ * stored order: for each k != i of S_i, k itself when it is a C point, then (whatever k's mark) every
+ * C point l != i of S_k in stored order; each candidate once, at its first occurrence, as column c(l).
+ * It is std_pattern's rule with C rows in place of F rows and every k as an intermediate point, and
+ * row-parallel in the same way (count, prefix, fill; per-thread row-stamped array).
+ * ====================================================================================== */
+static void agg_graph(const SSS_IMAT *S, const int *mark, SSS_IMAT *S2)
+{
+    const int n = S->num_rows;
+    const int *ia = S->row_ptr, *ja = S->col_idx;
+    int *cnum = (int *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(int));
+    int *crow = (int *)SSS_calloc((size_t)(n > 0 ? n : 1), sizeof(int));
+    int nc = 0;
+    for (int i = 0; i < n; ++i) {
+        cnum[i] = -1;
+        if (mark[i] == CGPT) cnum[i] = nc, crow[nc++] = i;
+    }
+    void *scr[kScratchMax];
+    const int T = scratch_alloc(sizeof(int) * (size_t)(n > 0 ? n : 1), scr);
+    int *rp = (int *)SSS_calloc((size_t)nc + 1, sizeof(int)), *ci = NULL;
+    for (int fill = 0; fill < 2; ++fill) {
+        if (fill) {
+            for (int c = 0; c < nc; ++c) rp[c + 1] += rp[c];
+            ci = (int *)SSS_calloc((size_t)(rp[nc] > 0 ? rp[nc] : 1), sizeof(int));
+        }
+#pragma omp parallel num_threads(T) if (nc > 4096)
+        {
+            int *seen = (int *)scr[omp_get_thread_num()];
+            for (int i = 0; i < n; ++i) seen[i] = -1;
+#pragma omp for schedule(dynamic, 1024)
+            for (int c = 0; c < nc; ++c) {
+                const int i = crow[c];
+                int cnt = 0, o = fill ? rp[c] : 0;
+                for (int q = ia[i]; q < ia[i + 1]; ++q) {
+                    const int k = ja[q];
+                    if (k == i) continue;
+                    if (mark[k] == CGPT && seen[k] != i) {
+                        seen[k] = i;
+                        if (fill) ci[o++] = cnum[k];
+                        cnt++;
+                    }
+                    for (int r = ia[k]; r < ia[k + 1]; ++r) {
+                        const int l = ja[r];
+                        if (l != i && mark[l] == CGPT && seen[l] != i) {
+                            seen[l] = i;
+                            if (fill) ci[o++] = cnum[l];
+                            cnt++;
+                        }
+                    }
+                }
+                if (!fill) rp[c + 1] = cnt;
+            }
+        }
+    }
+    scratch_free(scr, T);
+    free(cnum);
+    free(crow);
+    memset(S2, 0, sizeof(*S2));
+    S2->num_rows = S2->num_cols = nc;
+    S2->num_nnzs = rp[nc];
+    S2->row_ptr = rp;
+    S2->col_idx = ci;
+}
+
+static int agg_check(const SSS_IMAT *S, const int *mark)
+{
+    if (!S || !mark || S->num_rows <= 0 || !S->row_ptr) return ERROR_INPUT_PAR;
+    const int n = S->num_rows, nnz = S->row_ptr[n];
+    if (S->row_ptr[0] != 0 || nnz < 0 || (nnz > 0 && !S->col_idx)) return ERROR_INPUT_PAR;
+    for (int i = 0; i < n; ++i)
+        if (S->row_ptr[i + 1] < S->row_ptr[i]) return ERROR_DATA_STRUCTURE;
+    for (int q = 0; q < nnz; ++q)
+        if ((unsigned)S->col_idx[q] >= (unsigned)n) return ERROR_DATA_STRUCTURE;
+    return 0;
+}
+
+/* The host graph on a given compacted S and stage-one marks (tests; what the device graph is checked
+ * against).  S2 is written on success only; its arrays are the library's (SSS_imat_destroy). */
+int sss_agg_graph_host(const SSS_IMAT *S, const int *mark, SSS_IMAT *S2)
+{
+    if (!S2) return ERROR_INPUT_PAR;
+    const int rc = agg_check(S, mark);
+    if (rc) return rc;
+    agg_graph(S, mark, S2);
+    return 0;
+}
+
+/* The final marks: a stage-one C point stays C when stage two made it C or found its S2 row empty
+ * (ISPT: nobody to interpolate from), else it becomes F; every other point keeps its mark.  m2 is in
+ * the C numbering.  Returns the C-point count. */
+static int agg_final_marks(int n, int *mark, const int *m2)
+{
+    int c = 0, ncoarse = 0;
+    for (int i = 0; i < n; ++i) {
+        if (mark[i] != CGPT) continue;
+        if (m2[c] == CGPT || m2[c] == ISPT) ncoarse++;
+        else mark[i] = FGPT;
+        c++;
+    }
+    return ncoarse;
+}
+
+/* Whether S2 and the stage-two split of a level with nnz nonzeros in A go to the device: a device is
+ * present, SSS_SETUP_GPU_AGG is not 0 and nnz is at least SSS_SETUP_GPU_AGG_MIN (include/sss_hip.h). */
+static int agg_on_device(int nnz)
+{
+    const char *g = getenv("SSS_SETUP_GPU_AGG"), *gm = getenv("SSS_SETUP_GPU_AGG_MIN");
+    const int gpu_min = (gm && *gm) ? atoi(gm) : SSS_SETUP_GPU_AGG_MIN_DEFAULT;
+    return !(g && g[0] == '0') && nnz >= gpu_min && sss_hip_device_count() > 0;
+}
+
+/* Stage two on marks that hold the stage-one split of S: S2, the existing split on it, the final
+ * marks.  device: S2 may come from the GPU, and the split of S2 then follows its own SSS_SETUP_GPU_PMIS*
+ * switches on S2's entry count; the host runs on any error code.  Returns the C-point count (or <0). */
+static int agg_stage_two(const SSS_IMAT *S, int *mark, int device)
+{
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const char *gp = getenv("SSS_SETUP_GPU_PMIS"), *gpm = getenv("SSS_SETUP_GPU_PMIS_MIN");
+    const int pmis_min = (gpm && *gpm) ? atoi(gpm) : SSS_SETUP_GPU_PMIS_MIN_DEFAULT;
+    SSS_IMAT S2;
+    const double t0 = SSS_get_time();
+    /* the device graph is the host's, array for array (it prints its own timing line) */
+    if (!(device && sss_hip_agg_graph(S, mark, &S2) == 0)) {
+        agg_graph(S, mark, &S2);
+        if (timing)
+            fprintf(stderr, "[setup]   aggressive S2: host %.4f s, %d rows, %d entries\n", SSS_get_time() - t0, S2.num_rows,
+                    S2.num_nnzs);
+    }
+    const double t1 = SSS_get_time();
+    int *m2 = (int *)SSS_calloc((size_t)(S2.num_rows > 0 ? S2.num_rows : 1), sizeof(int));
+    int nc2 = 0, rounds = 0, on_device = 0, ncoarse;
+    if (device && !(gp && gp[0] == '0') && S2.num_nnzs >= pmis_min)
+        on_device = sss_hip_pmis(&S2, m2, &nc2, &rounds) == 0;
+    if (!on_device) nc2 = pmis_split(&S2, m2, &rounds);
+    if (timing)
+        fprintf(stderr, "[setup]   aggressive stage-two split: %s %.4f s, %d rounds, %d rows, %d entries\n",
+                on_device ? "device" : "host", SSS_get_time() - t1, rounds, S2.num_rows, S2.num_nnzs);
+    ncoarse = nc2 < 0 ? nc2 : agg_final_marks(S->num_rows, mark, m2);
+    free(m2);
+    SSS_imat_destroy(&S2);
+    return ncoarse;
+}
+
+/* The two-stage split on a given compacted S, on the host (tests).  mark and *ncoarse are written on
+ * success only. */
+int sss_pmis_agg_host(const SSS_IMAT *S, int *mark, int *ncoarse)
+{
+    int rc = agg_check(S, mark);
+    if (rc) return rc;
+    SSS_IMAT s = *S;
+    int *m = (int *)SSS_calloc((size_t)S->num_rows, sizeof(int));
+    rc = pmis_split(&s, m, NULL);
+    if (rc > 0) rc = agg_stage_two(S, m, 0);
+    if (rc >= 0) {
+        memcpy(mark, m, sizeof(int) * (size_t)S->num_rows);
+        if (ncoarse) *ncoarse = rc;
+    }
+    free(m);
+    return rc < 0 ? rc : 0;
+}
+
+/* Levels on which cs_type SSS_COARSE_PMIS_AGG is aggressive (SSS_SETUP_AGG_LEVELS, default 1, 0
+ * allowed): SSS_AMG_PARS keeps the reference's layout, so the count cannot live there. */
+static int agg_levels(void)
+{
+    const char *e = getenv("SSS_SETUP_AGG_LEVELS");
+    const int v = (e && *e) ? atoi(e) : 1;
+    return v > 0 ? v : 0;
+}
+
 /* Whether a level with nnz nonzeros in A takes the device pattern and weights: a device is present,
  * SSS_SETUP_GPU_INTERP is not 0 and nnz is at least SSS_SETUP_GPU_INTERP_MIN (include/sss_hip.h). */
 static int interp_on_device(int nnz)
@@ -771,21 +946,36 @@ static int interp_on_device(int nnz)
     return !(g && g[0] == '0') && nnz >= gpu_min && sss_hip_device_count() > 0;
 }
 
-int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
+/* SSS_amg_coarsen on level lvl of the hierarchy: cs_type SSS_COARSE_PMIS_AGG is aggressive on the
+ * first SSS_SETUP_AGG_LEVELS levels and SSS_COARSE_PMIS after them. */
+static int amg_coarsen_level(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars, int lvl)
 {
     int ncoarse = 0;
     const int timing = getenv("SSS_SETUP_TIMING") != NULL;
     const double t0 = SSS_get_time();
     strong_couplings(A, S, pars);
     const double t1 = SSS_get_time();
-    const int pmis = pars->cs_type == SSS_COARSE_PMIS;
-    const char *split = pmis ? "PMIS" : "RS";
+    const int agg = pars->cs_type == SSS_COARSE_PMIS_AGG && lvl < agg_levels();
+    const int pmis = pars->cs_type == SSS_COARSE_PMIS || pars->cs_type == SSS_COARSE_PMIS_AGG;
+    const char *split = agg ? "aggressive PMIS" : pmis ? "PMIS" : "RS";
     if (pars->cs_type == SSS_COARSE_RS) ncoarse = rs_split(A, S, vertices);
     else if (pmis) ncoarse = pmis_coarsen(S, vertices);
     else if (pars->cs_type != SSS_COARSE_RSP) SSS_exit_on_errcode(ERROR_AMG_COARSE_TYPE, __func__);
+    if (agg && ncoarse > 0) ncoarse = agg_stage_two(S, vertices->d, agg_on_device(A->num_nnzs));
     if (ncoarse <= 0) return ERROR_UNKNOWN;
     const double t2 = SSS_get_time();
-    if (pars->interp_type == intERP_DIR) {
+    if (agg || pars->interp_type == intERP_MPASS) {
+        /* multipass interpolation builds its pattern pass by pass with the weights (interp_MPASS):
+         * P leaves here with its sizes and no arrays, which is how SSS_amg_interp knows the level */
+        if (pars->interp_type < intERP_DIR || pars->interp_type > intERP_MPASS)
+            SSS_exit_on_errcode(ERROR_AMG_interp_type, __func__);
+        memset(P, 0, sizeof(*P));
+        P->num_rows = A->num_rows;
+        P->num_cols = ncoarse;
+        if (timing)
+            fprintf(stderr, "[setup]   coarsen: strength %.3f s, %s split %.3f s, multipass P follows\n", t1 - t0, split,
+                    t2 - t1);
+    } else if (pars->interp_type == intERP_DIR) {
         /* the F-F cleanup never runs after PMIS: it promotes until every strong F-F pair shares a
          * C point, which undoes the split (DESIGN.md "PMIS coarsening") */
         if (!pmis) ncoarse = cleanup_ff(S, vertices, A->num_rows, ncoarse);
@@ -811,6 +1001,12 @@ int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS
         SSS_exit_on_errcode(ERROR_AMG_interp_type, __func__);
     }
     return 0;
+}
+
+/* One level on its own is the finest one. */
+int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
+{
+    return amg_coarsen_level(A, vertices, P, S, pars, 0);
 }
 
 /* ======================================================================================
@@ -1239,9 +1435,236 @@ static void interp_EXTI(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S,
                 P->num_nnzs);
 }
 
+/*
+ * Multipass interpolation (interp_type intERP_MPASS and the aggressive levels of cs_type
+ * SSS_COARSE_PMIS_AGG; an engine extension after Stueben), on the final marks.
+ *
+ * Pass numbers: 0 for a C point; an F point gets 1 + the least number among the j != i of S_i that
+ * have one.  Sweep p gives p to every F point without a number that has a neighbour numbered p - 1
+ * (nobody numbered less is left among its neighbours, or it would have been numbered before), until a
+ * sweep numbers nobody.  F points never numbered and ISPT points keep empty rows of P.
+ *
+ * Row i of pass p >= 1, N_i = { j in S_i : j != i, pass(j) = p - 1 }: one walk of the stored entries
+ * (i, k) of A; d = the last stored diagonal entry, tot = the sum of the entries with k != i, sub = the
+ * sum of those with k in N_i, and for k in N_i the entries (k, c) of P in stored order: c joins the
+ * pattern at its first occurrence, hat w_c (from 0.0) receives a_ik p_kc.  Then
+ *   p_ic = -((tot / sub) hat w_c) / d,
+ * and all 0.0 when sub or d is 0.  No sign splitting; a row of A with zero sum gives a row of P with
+ * sum 1.  C rows hold one stored 1.0.  The rows of a pass are independent given the passes before it
+ * (per-thread scratch stamped with the row); they land in a staging pool, one block per pass, and are
+ * assembled into P in row order after the last pass.  Then the coarse renumbering and the truncation,
+ * as interp_STD.  Returns 0 or an error code with P untouched; *passes = the largest pass number.
+ */
+static int mpass_build(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, SSS_AMG_PARS *pars, int *passes,
+                       int *unreached)
+{
+    const int n = A->num_rows;
+    const int *ia = A->row_ptr, *ja = A->col_idx, *sa = S->row_ptr, *sj = S->col_idx;
+    const double *a = A->val;
+    const size_t ns = (size_t)(n > 0 ? n : 1);
+    int *pass = (int *)SSS_calloc(ns, sizeof(int)), *len = (int *)SSS_calloc(ns, sizeof(int));
+    int *todo = (int *)SSS_calloc(ns, sizeof(int)), *rows = (int *)SSS_calloc(ns, sizeof(int));
+    char *hit = (char *)SSS_calloc(ns, 1);
+    size_t *off = (size_t *)SSS_calloc(ns, sizeof(size_t)), pool = 0;
+    int *pc = NULL, ntodo = 0, left = 0, p = 0, rc = 0;
+    double *pv = NULL;
+
+    /* pass 0: the C rows */
+    for (int i = 0; i < n; ++i) {
+        pass[i] = -1;
+        if (mark[i] == CGPT) pass[i] = 0, len[i] = 1, off[i] = pool++;
+        else if (mark[i] == FGPT) todo[ntodo++] = i;
+        else left++;
+    }
+    pc = (int *)SSS_calloc(pool > 0 ? pool : 1, sizeof(int));
+    pv = (double *)SSS_calloc(pool > 0 ? pool : 1, sizeof(double));
+    for (int i = 0; i < n; ++i)
+        if (mark[i] == CGPT) pc[off[i]] = i, pv[off[i]] = 1.0;
+
+    /* per thread: seen, pos and ins (ints), n each, in one buffer */
+    void *scr[kScratchMax];
+    const int T = scratch_alloc(ns * 3 * sizeof(int), scr);
+    for (int t = 0; t < T; ++t) {
+        int *s = (int *)scr[t];
+        for (size_t c = 0; c < 3 * ns; ++c) s[c] = INT_MIN;
+    }
+    while (ntodo > 0) {
+        /* the rows of pass p + 1: in increasing i */
+        int nrows = 0, keep = 0;
+#pragma omp parallel for schedule(static) if (ntodo > 4096)
+        for (int t = 0; t < ntodo; ++t) {
+            const int i = todo[t];
+            char h = 0;
+            for (int q = sa[i]; q < sa[i + 1] && !h; ++q) h = sj[q] != i && pass[sj[q]] == p;
+            hit[t] = h;
+        }
+        for (int t = 0; t < ntodo; ++t) {
+            if (hit[t]) rows[nrows++] = todo[t];
+            else todo[keep++] = todo[t];
+        }
+        ntodo = keep;
+        if (nrows == 0) break;
+        p++;
+        /* count (the stamp is the row), offsets in the pool, fill (the stamp is ~row) */
+#pragma omp parallel num_threads(T) if (nrows > 1024)
+        {
+            int *seen = (int *)scr[omp_get_thread_num()], *ins = seen + 2 * ns;
+#pragma omp for schedule(dynamic, 256)
+            for (int t = 0; t < nrows; ++t) {
+                const int i = rows[t];
+                int cnt = 0;
+                for (int q = sa[i]; q < sa[i + 1]; ++q) ins[sj[q]] = i;
+                for (int j = ia[i]; j < ia[i + 1]; ++j) {
+                    const int k = ja[j];
+                    if (k == i || ins[k] != i || pass[k] != p - 1) continue;
+                    for (size_t q = off[k]; q < off[k] + (size_t)len[k]; ++q)
+                        if (seen[pc[q]] != i) seen[pc[q]] = i, cnt++;
+                }
+                len[i] = cnt;
+            }
+        }
+        const size_t old = pool;
+        for (int t = 0; t < nrows; ++t) off[rows[t]] = pool, pool += (size_t)len[rows[t]];
+        if (pool > (size_t)INT_MAX) {
+            rc = ERROR_MAT_SIZE;
+            break;
+        }
+        if (pool > old) {
+            pc = (int *)SSS_realloc(pc, pool * sizeof(int));
+            pv = (double *)SSS_realloc(pv, pool * sizeof(double));
+        }
+#pragma omp parallel num_threads(T) if (nrows > 1024)
+        {
+            int *seen = (int *)scr[omp_get_thread_num()], *pos = seen + ns, *ins = seen + 2 * ns;
+#pragma omp for schedule(dynamic, 256)
+            for (int t = 0; t < nrows; ++t) {
+                const int i = rows[t];
+                int *ci = pc + off[i], m = 0;
+                double *w = pv + off[i], d = 0.0, tot = 0.0, sub = 0.0;
+                for (int q = sa[i]; q < sa[i + 1]; ++q) ins[sj[q]] = i;
+                for (int j = ia[i]; j < ia[i + 1]; ++j) {
+                    const int k = ja[j];
+                    if (k == i) {
+                        d = a[j];
+                        continue;
+                    }
+                    tot += a[j];
+                    if (ins[k] != i || pass[k] != p - 1) continue;
+                    sub += a[j];
+                    for (size_t q = off[k]; q < off[k] + (size_t)len[k]; ++q) {
+                        const int c = pc[q];
+                        if (seen[c] != ~i) seen[c] = ~i, pos[c] = m, ci[m] = c, w[m++] = 0.0;
+                        w[pos[c]] += a[j] * pv[q];
+                    }
+                }
+                if (sub == 0.0 || d == 0.0) {
+                    for (int q = 0; q < m; ++q) w[q] = 0.0;
+                } else {
+                    const double f = tot / sub;
+                    for (int q = 0; q < m; ++q) w[q] = -(f * w[q]) / d;
+                }
+            }
+        }
+        /* the rows of this pass carry their number only now: nobody of the pass read it */
+        for (int t = 0; t < nrows; ++t) pass[rows[t]] = p;
+    }
+    scratch_free(scr, T);
+
+    if (rc == 0) {
+        SSS_MAT Q;
+        memset(&Q, 0, sizeof(Q));
+        Q.num_rows = n;
+        Q.row_ptr = (int *)SSS_calloc((size_t)n + 1, sizeof(int));
+        for (int i = 0; i < n; ++i) Q.row_ptr[i + 1] = Q.row_ptr[i] + len[i];
+        Q.num_nnzs = Q.row_ptr[n];
+        Q.col_idx = (int *)SSS_calloc((size_t)(Q.num_nnzs > 0 ? Q.num_nnzs : 1), sizeof(int));
+        Q.val = (double *)SSS_calloc((size_t)(Q.num_nnzs > 0 ? Q.num_nnzs : 1), sizeof(double));
+        /* coarse numbers of the columns while the rows are copied */
+        int *cmap = todo, ncoarse = 0;
+        for (int i = 0; i < n; ++i)
+            if (mark[i] == CGPT) cmap[i] = ncoarse++;
+        Q.num_cols = ncoarse;
+#pragma omp parallel for schedule(static) if (n > 65536)
+        for (int i = 0; i < n; ++i)
+            for (int q = 0; q < len[i]; ++q) {
+                Q.col_idx[Q.row_ptr[i] + q] = cmap[pc[off[i] + (size_t)q]];
+                Q.val[Q.row_ptr[i] + q] = pv[off[i] + (size_t)q];
+            }
+        SSS_amg_interp_trunc(&Q, pars);
+        *P = Q;
+        if (passes) *passes = p;
+        if (unreached) *unreached = ntodo + left;
+    }
+    free(pc);
+    free(pv);
+    free(off);
+    free(hit);
+    free(rows);
+    free(todo);
+    free(len);
+    free(pass);
+    return rc;
+}
+
+static int mpass_check(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, const SSS_MAT *P)
+{
+    if (!A || !P || !A->row_ptr) return ERROR_INPUT_PAR;
+    int rc = agg_check(S, mark);
+    if (rc) return rc;
+    const int n = S->num_rows;
+    if (A->num_rows != n || A->row_ptr[0] != 0) return ERROR_INPUT_PAR;
+    const int annz = A->row_ptr[n];
+    if (annz <= 0 || !A->col_idx || !A->val) return ERROR_INPUT_PAR;
+    for (int i = 0; i < n; ++i)
+        if (A->row_ptr[i + 1] < A->row_ptr[i]) return ERROR_DATA_STRUCTURE;
+    for (int q = 0; q < annz; ++q)
+        if ((unsigned)A->col_idx[q] >= (unsigned)n) return ERROR_DATA_STRUCTURE;
+    /* a strong column k != i of a row is in the row of A */
+    for (int i = 0; i < n; ++i)
+        for (int q = S->row_ptr[i]; q < S->row_ptr[i + 1]; ++q) {
+            int found = S->col_idx[q] == i;
+            for (int j = A->row_ptr[i]; j < A->row_ptr[i + 1] && !found; ++j) found = A->col_idx[j] == S->col_idx[q];
+            if (!found) return ERROR_DATA_STRUCTURE;
+        }
+    return 0;
+}
+
+/* The host multipass interpolation on a given A, compacted S and final marks (tests; what the device
+ * form is checked against).  P is written on success only (whatever it held is not freed); its
+ * arrays are the library's. */
+int sss_interp_mpass_host(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold,
+                          int *passes)
+{
+    const int rc = mpass_check(A, S, mark, P);
+    if (rc) return rc;
+    SSS_AMG_PARS pars;
+    memset(&pars, 0, sizeof(pars));
+    pars.trunc_threshold = trunc_threshold;
+    return mpass_build(A, S, mark, P, &pars, passes, NULL);
+}
+
+static void interp_MPASS(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
+{
+    const int timing = getenv("SSS_SETUP_TIMING") != NULL;
+    const double t0 = SSS_get_time();
+    int passes = 0, unreached = 0;
+    /* the device P (renumbered, truncated) is the host's bit for bit; on any error code P is untouched
+     * and the host computes it */
+    if (interp_on_device(A->num_nnzs) && sss_hip_interp_mpass(A, S, vertices->d, P, pars->trunc_threshold, &passes) == 0)
+        return;
+    const int rc = mpass_build(A, S, vertices->d, P, pars, &passes, &unreached);
+    if (rc) SSS_exit_on_errcode(rc, __func__);
+    if (timing)
+        fprintf(stderr, "[setup]   multipass P: host %.4f s, %d passes, %d rows unreached, %d rows, %d entries\n",
+                SSS_get_time() - t0, passes, unreached, P->num_rows, P->num_nnzs);
+}
+
 void SSS_amg_interp(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars)
 {
-    if (pars->interp_type == intERP_DIR) interp_DIR(A, vertices, P, pars);
+    /* a level whose P came from SSS_amg_coarsen without a pattern is a multipass level: interp_type
+     * intERP_MPASS, or an aggressive level of cs_type SSS_COARSE_PMIS_AGG whatever interp_type says */
+    if (pars->interp_type == intERP_MPASS || P->row_ptr == NULL) interp_MPASS(A, vertices, P, S, pars);
+    else if (pars->interp_type == intERP_DIR) interp_DIR(A, vertices, P, pars);
     else if (pars->interp_type == intERP_STD) interp_STD(A, vertices, P, S, pars);
     else if (pars->interp_type == intERP_EXTI) interp_EXTI(A, vertices, P, S, pars);
     else SSS_exit_on_errcode(ERROR_AMG_interp_type, __func__);
@@ -1505,7 +1928,7 @@ void sss_amg_setup_hooked(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars, sss_setup
         const double tc0 = SSS_get_time();
         sss_trace_push("SSS_amg_setup level %d", lvl);
         sss_trace_push("coarsen");
-        status = SSS_amg_coarsen(&L->A, &vertices, &L->P, &S, pars);
+        status = amg_coarsen_level(&L->A, &vertices, &L->P, &S, pars, lvl);
         sss_trace_pop();
         const double tc1 = SSS_get_time();
         if (status < 0) {

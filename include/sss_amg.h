@@ -113,8 +113,11 @@ typedef enum SSS_SM_TYPE_ {        /* SSS_main.h:133-145 */
 
 /* 1 and 2 are the reference's (SSS_main.h:147-152); intERP_EXTI is an engine extension: the extended+i
  * interpolation (De Sterck, Falgout, Nolting, Yang 2008) on the pattern of intERP_STD, the partner of
- * SSS_COARSE_PMIS.  SSS_SETUP_INTERP=exti makes SSS_amg_pars_init choose it. */
-typedef enum interp_type_ { intERP_DIR = 1, intERP_STD = 2, intERP_EXTI = 3 } interp_type;
+ * SSS_COARSE_PMIS.  SSS_SETUP_INTERP=exti makes SSS_amg_pars_init choose it.
+ * intERP_MPASS is an engine extension too: multipass interpolation (Stueben), the long-range partner of
+ * SSS_COARSE_PMIS_AGG, usable after any split; it builds its own pattern pass by pass.
+ * SSS_SETUP_INTERP=mpass makes SSS_amg_pars_init choose it. */
+typedef enum interp_type_ { intERP_DIR = 1, intERP_STD = 2, intERP_EXTI = 3, intERP_MPASS = 4 } interp_type;
 
 typedef struct SSS_RTN_ {          /* SSS_main.h:154-160; sizeof 24 */
     double ares;
@@ -124,8 +127,17 @@ typedef struct SSS_RTN_ {          /* SSS_main.h:154-160; sizeof 24 */
 
 /* 1 and 2 are the reference's; SSS_COARSE_PMIS is an engine extension: the parallel PMIS split
  * (no serial pass; on the GPU for large levels), meant for interp_type intERP_STD.
- * SSS_SETUP_COARSEN=pmis makes SSS_amg_pars_init choose it (cs_type 3, interp_type 2). */
-typedef enum SSS_COARSEN_TYPE_ { SSS_COARSE_RS = 1, SSS_COARSE_RSP = 2, SSS_COARSE_PMIS = 3 } SSS_COARSEN_TYPE;
+ * SSS_SETUP_COARSEN=pmis makes SSS_amg_pars_init choose it (cs_type 3, interp_type 2).
+ * SSS_COARSE_PMIS_AGG is aggressive coarsening: on the first SSS_SETUP_AGG_LEVELS
+ * levels (environment, default 1) a second PMIS split over the distance-two graph of the C points, with
+ * multipass interpolation whatever interp_type says; on every later level it is SSS_COARSE_PMIS.
+ * SSS_SETUP_COARSEN=pmis-agg makes SSS_amg_pars_init choose it (cs_type 4, interp_type 2). */
+typedef enum SSS_COARSEN_TYPE_ {
+    SSS_COARSE_RS = 1,
+    SSS_COARSE_RSP = 2,
+    SSS_COARSE_PMIS = 3,
+    SSS_COARSE_PMIS_AGG = 4
+} SSS_COARSEN_TYPE;
 
 typedef struct SSS_AMG_PARS_ {     /* SSS_main.h:170-194; sizeof 104 */
     int cycle_type;

@@ -188,6 +188,50 @@ int sss_hip_interp_exti(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SS
  * levels, and what the device pattern is tested against.  0 or an error code. */
 int sss_std_pattern_host(const SSS_IMAT *S, const int *mark, int ncoarse, SSS_MAT *P);
 
+/* Aggressive coarsening (cs_type SSS_COARSE_PMIS_AGG).  The distance-two graph S2 of the
+ * C points of a stage-one split: one row per point with mark CGPT, numbered c(i) in increasing i; row
+ * c(i) is one walk of S_i in stored order, for each k != i of S_i first k itself when it is a C point,
+ * then, whatever k's mark, every C point l != i of S_k in stored order; a candidate is kept at its first
+ * occurrence, in discovery order, as column c(l).  S2 gets num_rows = num_cols = the C points, row_ptr
+ * and col_idx (the library's arrays: SSS_imat_destroy), val NULL.  sss_hip_agg_graph builds it on the
+ * GPU (count, exclusive sum, fill; per-row hash tables as sss_hip_std_pattern, G lanes per row), array
+ * for array the host's.  Both return 0, or an error code with S2 untouched: ERROR_INPUT_PAR,
+ * ERROR_MAT_SIZE, ERROR_MISC (no device, a failed HIP call or copy), ERROR_DATA_STRUCTURE (an index out
+ * of range, a full table).  All argument checks precede the first HIP call.  With SSS_SETUP_TIMING one
+ * stderr line.  The setup uses the device graph, and then the device split of S2 under its own
+ * SSS_SETUP_GPU_PMIS* switches on S2's entries, when a device is present and A has at least
+ * SSS_SETUP_GPU_AGG_MIN nonzeros (default SSS_SETUP_GPU_AGG_MIN_DEFAULT = 10^7, the sibling switches'
+ * value); SSS_SETUP_GPU_AGG=0 keeps both on the host. */
+#define SSS_SETUP_GPU_AGG_MIN_DEFAULT 10000000
+int sss_agg_graph_host(const SSS_IMAT *S, const int *mark, SSS_IMAT *S2);
+int sss_hip_agg_graph(const SSS_IMAT *S, const int *mark, SSS_IMAT *S2);
+/* The two-stage split on the host: the PMIS split of S, the PMIS split of S2, and the final marks (a
+ * stage-one C point stays C when stage two made it C or its S2 row is empty, else it becomes F).  mark
+ * (n ints) and *ncoarse are written on success only.  0 or an error code. */
+int sss_pmis_agg_host(const SSS_IMAT *S, int *mark, int *ncoarse);
+/* Multipass interpolation (interp_type intERP_MPASS; the rule: amg_amd/host/sss_setup.c mpass_build,
+ * DESIGN.md 6.8) from A, a compacted S and the final marks, on the host (OpenMP, row-parallel per
+ * pass): the pattern and the weights pass by pass, the coarse renumbering of the columns, the
+ * truncation.  P (whatever it held is ignored, not freed) gets the library's arrays; *passes = the
+ * largest pass number.  0, or an error code with P untouched. */
+int sss_interp_mpass_host(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold,
+                          int *passes);
+/* The same on the GPU, bit for bit the host's P.  The pass numbers come from relaxation sweeps steered by
+ * the host; then one round of ordinary launches per pass over that pass's rows, G lanes (1, 4, 16 or 64,
+ * from the pass's average candidate bound, the entries of the rows of P of N_i) per row: first
+ * occurrences by an atomicMin of the sequence number in the row's hash table, hat w in the same table
+ * with one owner lane per slot and the terms handed over in walk order; d, tot and sub on every lane.
+ * A pass writes its rows into a block of its own and reads the block of the pass before; P is assembled
+ * in row order after the last pass, then renumbered and truncated as in sss_hip_interp_std.  Tables sit
+ * in LDS, or in a global array allocated inside the call when a row's bound does not fit
+ * (SSS_HIP_INTERP_LDS_SLOTS, SSS_HIP_INTERP_LANES as there).  Both forms want every strong column k != i
+ * of a row present in the row of A.  Returns 0, or an error code with P untouched: ERROR_INPUT_PAR,
+ * ERROR_MAT_SIZE, ERROR_MISC, ERROR_DATA_STRUCTURE; all argument checks precede the first HIP call.  The
+ * setup uses it under the switches of sss_hip_interp_std (SSS_SETUP_GPU_INTERP, SSS_SETUP_GPU_INTERP_MIN)
+ * and runs the host form on any error code.  With SSS_SETUP_TIMING one stderr line. */
+int sss_hip_interp_mpass(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold,
+                         int *passes);
+
 /* Progress hook of the setup (amg_amd/host/sss_setup.c): hook(ctx, mg, done, 0) once levels
  * 0 .. done-1 are final and none of them is the coarsest; hook(ctx, mg, num_levels - 1, 1) at
  * the end. */
