@@ -8,6 +8,6 @@ from ._native import (  # noqa: F401
     SSS_AMG, SSS_AMG_COMP,
     SSS_AMG_PARS, SSS_HIP_OPTS, SSS_MAT, SSS_RTN, SSS_SMTR, SSS_VEC, coarse_last, csr_arrays, default_pars, device_count,
     hbm_used_bytes, level_step, spmv_enc,
-    agg_graph, generate, interp_exti, interp_mpass, interp_std, lib, part_save, pmis, pmis_agg, rap_values, read_mtx, std_pattern,
+    agg_graph, generate, interp_exti, interp_mpass, interp_std, interp_trunc, lib, part_save, pmis, pmis_agg, rap_values, read_mtx, setup_pmax, std_pattern,
 )
 from .workloads import convdiff_csr  # noqa: F401

@@ -131,7 +131,7 @@ ABI_SYMBOLS = [
     "sss_hip_rap_values", "sss_rap_values_host", "SSS_amg_refresh", "sss_hip_hier_refresh",
     "sss_hip_std_pattern", "sss_std_pattern_host", "sss_hip_interp_std", "sss_hip_interp_exti",
     "sss_agg_graph_host", "sss_hip_agg_graph", "sss_pmis_agg_host", "sss_interp_mpass_host",
-    "sss_hip_interp_mpass",
+    "sss_hip_interp_mpass", "sss_setup_pmax", "sss_interp_trunc_host", "sss_hip_interp_trunc",
     "sss_hip_upload_vec", "sss_hip_download_vec", "sss_hip_cycle", "sss_hip_residual_norm", "sss_hip_pcg",
     "sss_hip_fgmres", "sss_hip_host_orth", "sss_hip_host_pcg_update", "sss_hip_host_dot2",
     "SSS_amg_save", "SSS_amg_load",
@@ -226,6 +226,9 @@ def _declare(lib):
         "sss_pmis_agg_host": (C.c_int, [P(SSS_IMAT), _int_p, _int_p]),
         "sss_interp_mpass_host": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double, _int_p]),
         "sss_hip_interp_mpass": (C.c_int, [P(SSS_MAT), P(SSS_IMAT), _int_p, P(SSS_MAT), C.c_double, _int_p]),
+        "sss_setup_pmax": (C.c_int, []),
+        "sss_interp_trunc_host": (C.c_int, [P(SSS_MAT), C.c_double, C.c_int]),
+        "sss_hip_interp_trunc": (C.c_int, [P(SSS_MAT), C.c_double, C.c_int]),
         "SSS_mat_struct_create": (SSS_MAT, [C.c_int, C.c_int, C.c_int]),
         "sss_hip_upload_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
         "sss_hip_download_vec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dbl_p, C.c_int]),
@@ -488,6 +491,42 @@ def interp_mpass(A_csr, S_csr, mark, trunc: float, device: bool = False):
         raise err
     try:
         return (*csr_arrays(P), P.num_cols, passes.value)
+    finally:
+        lib().SSS_mat_destroy(C.byref(P))
+
+
+def setup_pmax() -> int:
+    """The cap on the entries per row of P the setup runs with (SSS_SETUP_PMAX; 0 = off)."""
+    return int(lib().sss_setup_pmax())
+
+
+def interp_trunc(P_csr, ncols: int, trunc: float, pmax: int, device: bool = False):
+    """Truncation of an interpolation matrix P_csr = (row_ptr, col_idx, val) with `ncols` columns (already
+    in coarse numbering) at the relative threshold `trunc`, with at most `pmax` entries per row (0: no cap;
+    the rule: DESIGN.md 6.9).  Returns (row_ptr, col_idx, val, ncols), from the host
+    (sss_interp_trunc_host) or from the GPU (sss_hip_interp_trunc), which are equal bit for bit.  Raises
+    RuntimeError with the error code (.rc) when it fails; P is then untouched (.untouched)."""
+    prp = np.ascontiguousarray(P_csr[0], dtype=np.int32)
+    pci = np.ascontiguousarray(P_csr[1], dtype=np.int32)
+    pv = np.ascontiguousarray(P_csr[2], dtype=np.float64)
+    n = len(prp) - 1
+    # the truncation frees P's arrays: they must be the library's, not numpy's
+    P = lib().SSS_mat_struct_create(n, ncols, len(pci))
+    C.memmove(P.row_ptr, prp.ctypes.data, prp.nbytes)
+    if len(pci):
+        C.memmove(P.col_idx, pci.ctypes.data, pci.nbytes)
+        C.memmove(P.val, pv.ctypes.data, pv.nbytes)
+    try:
+        fn = lib().sss_hip_interp_trunc if device else lib().sss_interp_trunc_host
+        rc = fn(C.byref(P), trunc, pmax)
+        if rc != 0:
+            got = csr_arrays(P)
+            err = RuntimeError(f"truncation failed ({rc})")
+            err.rc = rc
+            err.untouched = (P.num_nnzs == len(pci) and np.array_equal(got[0], prp) and np.array_equal(got[1], pci)
+                             and np.array_equal(got[2].view(np.uint64), pv.view(np.uint64)))
+            raise err
+        return (*csr_arrays(P), P.num_cols)
     finally:
         lib().SSS_mat_destroy(C.byref(P))
 

@@ -20,6 +20,9 @@
 //            strong F neighbour k has row k of A walked twice by the group, first for den, then for the
 //            terms f a_kl, the qualifying entries of a chunk taken lane by lane from an in-order ballot.
 //            d and den are computed by every lane of the group.
+//   cap      the truncation with at most pmax entries per row (SSS_SETUP_PMAX): the cut of a
+//            capped row is found in pmax rounds of a group-wide arg-max, the sums the host makes in stored
+//            order are made in stored order by every lane of the group from the same values.
 //
 // The table of a row is in LDS when the row's candidate bound (its S row plus the S rows of its strong
 // F neighbours) fits the group's share of it, else in a global array sized from the bound inside the
@@ -35,6 +38,7 @@
 #include <climits>
 #include <initializer_list>
 #include <cstring>
+#include <string>
 
 namespace sss {
 
@@ -1139,6 +1143,128 @@ __global__ __launch_bounds__(kBlock) void trunc_rows(int n, int pnnz, const int 
     }
 }
 
+// The truncation with the cap on the entries per row (pmax > 0; the rule: amg_amd/host/sss_setup.c
+// trunc_cut and interp_trunc_par), G lanes per row.  The thresholds and the number of
+// survivors come from strided walks and shuffle reductions (max, min and a count do not depend on
+// order).  A row with more than pmax survivors is cut in pmax rounds: each round is the group-wide
+// arg-max of the key (|v|, then the smaller position) over the survivors strictly after the previous
+// round's pick in that order, every lane over its stride and then log2 G shuffle steps; the last pick is
+// the cut.  Nothing is kept per entry and no array is indexed per lane.  What the host sums in stored
+// order (pos_sum, neg_sum, pos_kept, neg_kept) every lane of the group sums in stored order from the
+// same values, G loaded at a time and handed round by shuffles.  FILL false: the kept count into cnt[i].
+// FILL true: the kept entries in stored order at nrp[i], offsets from an in-order ballot of the group.
+// Loops are bounded by the row length or pmax; writes are bounded by the row's room in the new arrays.
+__device__ __forceinline__ bool trunc_kept(double v, int k, double tp, double tn, bool capped, double cut_a, int cut_k)
+{
+    const double a = fabs(v);
+    return (v >= tp || v <= tn) && (!capped || a > cut_a || (a == cut_a && k <= cut_k));
+}
+
+template <int G, bool FILL>
+__global__ __launch_bounds__(kBlock) void trunc_rows_cap(int n, int pnnz, const int *__restrict__ prp,
+                                                         const int *__restrict__ pci, const double *__restrict__ pv,
+                                                         double eps, int pmax, int *__restrict__ cnt,
+                                                         const int *__restrict__ nrp, int kept, int *__restrict__ nci,
+                                                         double *__restrict__ nv)
+{
+    const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+    const long long row = (long long)blockIdx.x * (kBlock / G) + grp;
+    if (row >= n) return;   // the whole group leaves
+    const int i = (int)row;
+    const int lo = max(prp[i], 0), hi = max(min(prp[i + 1], pnnz), lo);
+    // thresholds
+    double tp = 0, tn = 0;
+    for (int k = lo + gl; k < hi; k += G) {
+        const double v = pv[k];
+        if (v > 0) tp = tp > v ? tp : v;
+        else if (v < 0) tn = tn < v ? tn : v;
+    }
+    for (int o = G / 2; o > 0; o >>= 1) {
+        const double a = __shfl_xor(tp, o, G), b = __shfl_xor(tn, o, G);
+        tp = tp > a ? tp : a;
+        tn = tn < b ? tn : b;
+    }
+    tp *= eps;
+    tn *= eps;
+    // survivors
+    int ns = 0;
+    for (int k = lo + gl; k < hi; k += G) ns += (pv[k] >= tp) || (pv[k] <= tn);
+    for (int o = G / 2; o > 0; o >>= 1) ns += __shfl_xor(ns, o, G);
+    const bool capped = ns > pmax;
+    if (!FILL) {
+        if (gl == 0) cnt[i] = capped ? pmax : ns;
+        return;
+    }
+    // the cut of a capped row: pmax rounds
+    double cut_a = 0.0;
+    int cut_k = -1;
+    if (capped) {
+        for (int r = 0; r < pmax; ++r) {
+            double ba = -1.0;
+            int bk = -1;
+            for (int k = lo + gl; k < hi; k += G) {
+                const double v = pv[k], a = fabs(v);
+                if (!(v >= tp || v <= tn)) continue;
+                if (r > 0 && !(a < cut_a || (a == cut_a && k > cut_k))) continue;   // picked by an earlier round
+                if (a > ba) ba = a, bk = k;   // k grows: on ties the earlier position stays
+            }
+            for (int o = G / 2; o > 0; o >>= 1) {
+                const double oa = __shfl_xor(ba, o, G);
+                const int ok = __shfl_xor(bk, o, G);
+                if (ok >= 0 && (bk < 0 || oa > ba || (oa == ba && ok < bk))) ba = oa, bk = ok;
+            }
+            if (bk < 0) break;   // the same on every lane
+            cut_a = ba;
+            cut_k = bk;
+        }
+    }
+    // pos_sum and neg_sum in stored order; the kept columns and pos_kept, neg_kept in stored order
+    const int o0 = max(nrp[i], 0), room = min(nrp[i + 1], kept) - o0;
+    double pos_sum = 0, neg_sum = 0, pos_kept = 0, neg_kept = 0;
+    int o = 0;
+    for (int k0 = lo; k0 < hi; k0 += G) {
+        const int k = k0 + gl, m = min(G, hi - k0);
+        const double v = k < hi ? pv[k] : 0.0;
+        for (int t = 0; t < m; ++t) {
+            const double vt = __shfl(v, t, G);
+            if (vt > 0) pos_sum += vt;
+            else if (vt < 0) neg_sum += vt;
+        }
+        const bool keep = k < hi && trunc_kept(v, k, tp, tn, capped, cut_a, cut_k);
+        const unsigned long long mask = group_ballot<G>(keep, gl);
+        if (keep) {
+            const int w = o + __popcll(mask & ((1ull << gl) - 1ull));
+            if (w < room) nci[o0 + w] = pci[k];
+        }
+        for (unsigned long long b = mask; b; b &= b - 1) {
+            const double vt = __shfl(v, __ffsll((long long)b) - 1, G);
+            if (vt >= tp) pos_kept += vt;
+            else neg_kept += vt;
+        }
+        o += __popcll(mask);
+    }
+    const bool pos_has = pos_kept > SMALLFLOAT, neg_has = neg_kept < -SMALLFLOAT;
+    double pos_fac = pos_has ? pos_sum / pos_kept : 1.0;
+    double neg_fac = neg_has ? neg_sum / neg_kept : 1.0;
+    if (capped) {
+        // a class the cap removed entirely hands its sum to the other one
+        if (pos_sum > 0 && !pos_has && neg_has) neg_fac = (pos_sum + neg_sum) / neg_kept;
+        if (neg_sum < 0 && !neg_has && pos_has) pos_fac = (pos_sum + neg_sum) / pos_kept;
+    }
+    o = 0;
+    for (int k0 = lo; k0 < hi; k0 += G) {
+        const int k = k0 + gl;
+        const double v = k < hi ? pv[k] : 0.0;
+        const bool keep = k < hi && trunc_kept(v, k, tp, tn, capped, cut_a, cut_k);
+        const unsigned long long mask = group_ballot<G>(keep, gl);
+        if (keep) {
+            const int w = o + __popcll(mask & ((1ull << gl) - 1ull));
+            if (w < room) nv[o0 + w] = v >= tp ? v * pos_fac : v * neg_fac;
+        }
+        o += __popcll(mask);
+    }
+}
+
 int copy_sync(void *dst, const void *src, size_t bytes, hipMemcpyKind k, hipStream_t st)
 {
     if (bytes == 0) return 0;
@@ -1181,6 +1307,9 @@ struct Dev {
     hipStream_t st = nullptr;
     std::vector<void *> mem;
     double t_copy = 0.0, t_kern = 0.0, t_last = PhaseTimer::now();
+    double t_trunc = 0.0;        // seconds of the truncation, when it was timed
+    int cap = 0, cap_lanes = 0;  // the cap on the entries per row the truncation ran with, its lanes per row
+    bool trunc_timed = false;
     bool oom = false;
     ~Dev()
     {
@@ -1299,11 +1428,23 @@ int make_tables(Dev &d, Tables &t, const SSS_IMAT *S, const int *mark, const int
     return 0;
 }
 
+// what a timing line says about the cap on the entries per row: nothing unless the truncation was timed
+// (in a setup: when SSS_SETUP_PMAX is set; set to 0 the cap is off and the note gives the uncapped seconds)
+std::string cap_note(const Dev &d)
+{
+    if (!d.trunc_timed) return "";
+    char buf[128];
+    if (d.cap > 0) snprintf(buf, sizeof buf, ", cap %d at %d lanes per row, truncation %.4f s", d.cap, d.cap_lanes, d.t_trunc);
+    else snprintf(buf, sizeof buf, ", no cap, truncation %.4f s", d.t_trunc);
+    return buf;
+}
+
 void timing_line(const char *step, const Dev &d, const Tables &t, int rows, int nnz, const char *rule = "standard")
 {
     if (getenv("SSS_SETUP_TIMING"))
         fprintf(stderr, "[setup]   %s P: device %s, %d rows, %d entries, %d lanes per row, %d rows on global tables, "
-                        "copies %.4f s, kernels %.4f s\n", rule, step, rows, nnz, t.G, t.global_rows, d.t_copy, d.t_kern);
+                        "copies %.4f s, kernels %.4f s%s\n", rule, step, rows, nnz, t.G, t.global_rows, d.t_copy, d.t_kern,
+                cap_note(d).c_str());
 }
 
 template <class T>
@@ -1476,35 +1617,66 @@ extern "C" int sss_hip_std_pattern(const SSS_IMAT *S, const int *mark, int ncoar
     return 0;
 }
 
-// The tail of every interpolation: the coarse numbers of the columns of (prp, pci, pv), the truncation,
-// the download.  P is written after the last copy only; `replace` frees the arrays it held.
-static int renumber_truncate(Dev &d, const Tables &t, const char *what, int n, const int *prp, int *pci, const double *pv,
-                             int pnnz, double trunc_threshold, SSS_MAT *P, bool replace)
+template <bool FILL, class... Args>
+static void launch_trunc_cap(int G, hipStream_t st, int n, Args... a)
 {
-    int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
+    switch (G) {
+    case 1: hipLaunchKernelGGL((trunc_rows_cap<1, FILL>), dim3(grid_for(n)), dim3(kBlock), 0, st, a...); break;
+    case 4: hipLaunchKernelGGL((trunc_rows_cap<4, FILL>), dim3(grid_for(4LL * n)), dim3(kBlock), 0, st, a...); break;
+    case 16: hipLaunchKernelGGL((trunc_rows_cap<16, FILL>), dim3(grid_for(16LL * n)), dim3(kBlock), 0, st, a...); break;
+    default: hipLaunchKernelGGL((trunc_rows_cap<64, FILL>), dim3(grid_for(64LL * n)), dim3(kBlock), 0, st, a...); break;
+    }
+}
+
+// The truncation of (prp, pci, pv) on the device at threshold eps with at most pmax entries per row
+// (0: no cap, one lane per row): count, prefix, fill.  *nrp, *nci, *nv are the new arrays, *kept their entries;
+// `timing` measures it on its own (a stream synchronisation before and after).
+static int truncate_rows(Dev &d, int n, const int *prp, const int *pci, const double *pv, int pnnz, double eps, int pmax,
+                         bool timing, int **nrp_out, int **nci_out, double **nv_out, int *kept_out)
+{
     int *cnt = d.alloc<int>((size_t)n + 1), *nrp = d.alloc<int>((size_t)n + 1);
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
+    double t0 = 0.0;
+    d.trunc_timed = timing;
+    if (timing) {
+        SSS_HIP(hipStreamSynchronize(d.st));
+        t0 = PhaseTimer::now();
+    }
+    // lanes per row of the capped kernels from the mean row of the untruncated P
+    const int G = pmax > 0 ? lanes_for_candidates((double)pnnz / (double)std::max(n, 1)) : 1;
+    d.cap = pmax, d.cap_lanes = G;
     SSS_HIP(hipMemsetAsync(cnt + n, 0, sizeof(int), d.st));
-    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
-    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
-    if (pnnz > 0) hipLaunchKernelGGL(renumber, dim3(grid_for(pnnz)), dim3(kBlock), 0, d.st, pnnz, n, cmap, pci, t.ctr);
-    hipLaunchKernelGGL((trunc_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
-                       nrp, 0, nullptr, nullptr);
+    if (pmax > 0)
+        launch_trunc_cap<false>(G, d.st, n, n, pnnz, prp, pci, pv, eps, pmax, cnt, (const int *)nrp, 0, (int *)nullptr,
+                                (double *)nullptr);
+    else
+        hipLaunchKernelGGL((trunc_rows<false>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, eps, cnt, nrp, 0,
+                           nullptr, nullptr);
     if (int rc = exclusive_sum(d, cnt, nrp, (size_t)n + 1)) return rc;
-    int h_ctr[2], kept = 0, ncoarse = 0;
-    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    int kept = 0;
+    SSS_HIP(hipGetLastError());
     if (copy_sync(&kept, nrp + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
-    if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
     if (kept < 0 || kept > pnnz) return ERROR_MAT_SIZE;
     int *nci = d.alloc<int>((size_t)kept);
     double *nv = d.alloc<double>((size_t)kept);
     if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
-    hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, trunc_threshold, cnt,
-                       nrp, kept, nci, nv);
-    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
-    d.lap(false);
+    if (pmax > 0)
+        launch_trunc_cap<true>(G, d.st, n, n, pnnz, prp, pci, pv, eps, pmax, cnt, (const int *)nrp, kept, nci, nv);
+    else
+        hipLaunchKernelGGL((trunc_rows<true>), dim3(grid_for(n)), dim3(kBlock), 0, d.st, n, pnnz, prp, pci, pv, eps, cnt, nrp, kept,
+                           nci, nv);
+    SSS_HIP(hipGetLastError());
+    if (timing) {
+        SSS_HIP(hipStreamSynchronize(d.st));
+        d.t_trunc = PhaseTimer::now() - t0;
+    }
+    *nrp_out = nrp, *nci_out = nci, *nv_out = nv, *kept_out = kept;
+    return 0;
+}
 
-    // into arrays of its own first: P stays untouched if a copy fails
+// (nrp, nci, nv) into P: into arrays of its own first, so that P stays untouched if a copy fails
+static int download_p(Dev &d, int n, const int *nrp, const int *nci, const double *nv, int kept, SSS_MAT *P, bool replace)
+{
     HostArr<int> rp((size_t)n + 1), ci((size_t)kept);
     HostArr<double> val((size_t)kept);
     if (copy_sync(rp.p, nrp, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
@@ -1519,11 +1691,65 @@ static int renumber_truncate(Dev &d, const Tables &t, const char *what, int n, c
         memset(P, 0, sizeof(*P));
         P->num_rows = n;
     }
-    P->num_cols = ncoarse;
     P->num_nnzs = kept;
     P->row_ptr = rp.release();
     P->col_idx = ci.release();
     P->val = val.release();
+    return 0;
+}
+
+// The tail of every interpolation: the coarse numbers of the columns of (prp, pci, pv), the truncation
+// (with the cap of SSS_SETUP_PMAX), the download.  P is written after the last copy only; `replace` frees
+// the arrays it held.
+static int renumber_truncate(Dev &d, const Tables &t, const char *what, int n, const int *prp, int *pci, const double *pv,
+                             int pnnz, double trunc_threshold, SSS_MAT *P, bool replace)
+{
+    int *cmap = d.alloc<int>((size_t)n + 1), *flag = d.alloc<int>((size_t)n + 1);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
+    hipLaunchKernelGGL(flag_coarse, dim3(grid_for((long long)n + 1)), dim3(kBlock), 0, d.st, n, t.mark, flag);
+    if (int rc = exclusive_sum(d, flag, cmap, (size_t)n + 1)) return rc;
+    if (pnnz > 0) hipLaunchKernelGGL(renumber, dim3(grid_for(pnnz)), dim3(kBlock), 0, d.st, pnnz, n, cmap, pci, t.ctr);
+    int *nrp = nullptr, *nci = nullptr, h_ctr[2], kept = 0, ncoarse = 0;
+    double *nv = nullptr;
+    if (int rc = truncate_rows(d, n, prp, pci, pv, pnnz, trunc_threshold, sss_setup_pmax(),
+                               getenv("SSS_SETUP_TIMING") && getenv("SSS_SETUP_PMAX"), &nrp, &nci, &nv, &kept))
+        return rc;
+    if (int rc = read_flags(d, t, what, h_ctr)) return rc;
+    if (copy_sync(&ncoarse, cmap + n, sizeof(int), hipMemcpyDeviceToHost, d.st)) return ERROR_MISC;
+    d.lap(false);
+    if (int rc = download_p(d, n, nrp, nci, nv, kept, P, replace)) return rc;
+    P->num_cols = ncoarse;
+    return 0;
+}
+
+extern "C" int sss_hip_interp_trunc(SSS_MAT *P, double eps, int pmax)
+{
+    if (pmax < 0 || !P || P->num_rows <= 0 || !P->row_ptr || P->row_ptr[0] != 0) return ERROR_INPUT_PAR;
+    const int n = P->num_rows, pnnz = P->row_ptr[n];
+    for (int i = 0; i < n; ++i)
+        if (P->row_ptr[i + 1] < P->row_ptr[i]) return ERROR_INPUT_PAR;
+    if (pnnz != P->num_nnzs || (pnnz > 0 && (!P->col_idx || !P->val))) return ERROR_INPUT_PAR;
+    // n * 64 lanes must fit the grid (2^31 - 1 blocks)
+    if ((long long)n * 64 / kBlock >= 0x7fffffffLL) return ERROR_MAT_SIZE;
+    if (sss_hip_device_count() <= 0) return ERROR_MISC;
+    Dev d;
+    if (hipStreamCreateWithFlags(&d.st, hipStreamNonBlocking) != hipSuccess) return ERROR_MISC;
+    const int *prp = d.upload(P->row_ptr, (size_t)n + 1), *pci = d.upload(P->col_idx, (size_t)pnnz);
+    const double *pv = d.upload(P->val, (size_t)pnnz);
+    if (d.oom) return hip_fail(hipErrorOutOfMemory, "hipMalloc(truncation)", __FILE__, __LINE__);
+    d.lap(true);
+    int *nrp = nullptr, *nci = nullptr, kept = 0;
+    double *nv = nullptr;
+    if (int rc = truncate_rows(d, n, prp, pci, pv, pnnz, eps, pmax, getenv("SSS_SETUP_TIMING") != nullptr, &nrp, &nci, &nv, &kept))
+        return rc;
+    SSS_HIP(hipStreamSynchronize(d.st));
+    d.lap(false);
+    const int ncols = P->num_cols;
+    if (int rc = download_p(d, n, nrp, nci, nv, kept, P, true)) return rc;
+    P->num_cols = ncols;
+    if (getenv("SSS_SETUP_TIMING"))
+        fprintf(stderr, "[setup]   truncation: device, %d rows, %d of %d entries kept, copies %.4f s, kernels %.4f s%s\n", n, kept,
+                pnnz, d.t_copy, d.t_kern, cap_note(d).c_str());
     return 0;
 }
 
@@ -1676,8 +1902,8 @@ extern "C" int sss_hip_interp_mpass(const SSS_MAT *A, const SSS_IMAT *S, const i
     if (passes) *passes = npass;
     if (getenv("SSS_SETUP_TIMING"))
         fprintf(stderr, "[setup]   multipass P: device, %d passes, %lld rows unreached, %d rows, %d entries, up to %d lanes per row, "
-                        "%d rows on global tables, copies %.4f s, kernels %.4f s\n", npass, (long long)n - numbered, n, P->num_nnzs,
-                max_lanes, global_rows_all, d.t_copy, d.t_kern);
+                        "%d rows on global tables, copies %.4f s, kernels %.4f s%s\n", npass, (long long)n - numbered, n, P->num_nnzs,
+                max_lanes, global_rows_all, d.t_copy, d.t_kern, cap_note(d).c_str());
     return 0;
 }
 

@@ -390,6 +390,8 @@ void SSS_amg_pars_print(SSS_AMG_PARS *pars)
     printf("AMG dof on coarsest grid:          %d\n", pars->coarse_dof);
     printf("AMG strong threshold:              %.4lf\n", pars->strong_threshold);
     printf("AMG truncation threshold:          %.4lf\n", pars->trunc_threshold);
+    /* the cap on the entries per row of P (SSS_SETUP_PMAX): a line of its own, only when it is on */
+    if (sss_setup_pmax() > 0) printf("AMG max entries per row of P:      %d\n", sss_setup_pmax());
     printf("AMG max row sum:                   %.4lf\n", pars->max_row_sum);
     fputs(rule, stdout);
 }

@@ -1012,13 +1012,68 @@ int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS
 /* ======================================================================================
  * Interpolation and truncation
  * ====================================================================================== */
+/* The cap on the entries per row of P (SSS_SETUP_PMAX, 0 = off; include/sss_hip.h): SSS_AMG_PARS keeps
+ * the reference's layout, so the value cannot live there. */
+int sss_setup_pmax(void)
+{
+    const char *e = getenv("SSS_SETUP_PMAX");
+    const int v = (e && *e) ? atoi(e) : 0;
+    return v > 0 ? v : 0;
+}
+
+/* Whether the cap cuts row [lo, hi) of val, whose thresholds are tp and tn: it does when more than pmax
+ * entries survive them.  Then (*cut_a, *cut_k) is the key (|v|, stored position) of the pmax-th survivor
+ * in the order "larger |v| first, earlier position on ties": the kept entries are the survivors at or
+ * before it in that order.  Found in pmax rounds, each the largest key strictly after the previous
+ * round's pick, so that nothing is stored per entry (the device kernel does the same rounds). */
+static int trunc_cut(const double *val, int lo, int hi, double tp, double tn, int pmax, double *cut_a, int *cut_k)
+{
+    int survivors = 0;
+    if (pmax <= 0) return 0;
+    for (int k = lo; k < hi; ++k) survivors += (val[k] >= tp) || (val[k] <= tn);
+    if (survivors <= pmax) return 0;
+    double pa = 0.0;
+    int pk = -1;
+    for (int r = 0; r < pmax; ++r) {
+        double ba = -1.0;
+        int bk = -1;
+        for (int k = lo; k < hi; ++k) {
+            const double v = val[k], a = fabs(v);
+            if (!(v >= tp || v <= tn)) continue;
+            if (r > 0 && !(a < pa || (a == pa && k > pk))) continue;   /* picked by an earlier round */
+            if (a > ba) { ba = a; bk = k; }                             /* ties: the earlier position stays */
+        }
+        if (bk < 0) break;
+        pa = ba;
+        pk = bk;
+    }
+    *cut_a = pa;
+    *cut_k = pk;
+    return 1;
+}
+
+/* The factors of a capped row: the SMALLFLOAT rule, and a class the cap removed entirely hands its sum
+ * to the other one, so that the row sum of P survives the cap. */
+static void trunc_capped_factors(double pos_sum, double neg_sum, double pos_kept, double neg_kept, double *pos_fac,
+                                 double *neg_fac)
+{
+    const int pos_has = pos_kept > SMALLFLOAT, neg_has = neg_kept < -SMALLFLOAT;
+    *pos_fac = pos_has ? pos_sum / pos_kept : 1.0;
+    *neg_fac = neg_has ? neg_sum / neg_kept : 1.0;
+    if (pos_sum > 0 && !pos_has && neg_has) *neg_fac = (pos_sum + neg_sum) / neg_kept;
+    if (neg_sum < 0 && !neg_has && pos_has) *pos_fac = (pos_sum + neg_sum) / pos_kept;
+}
+
+#define TRUNC_KEPT(v, k) (((v) >= pos_max || (v) <= neg_min) && \
+                          (!capped || fabs(v) > cut_a || (fabs(v) == cut_a && (k) <= cut_k)))
+
 /* Per-row form of the truncation below for large P: the same kept entries and scaled values,
  * computed row-parallel into new arrays (kept counts, prefix, fill). */
-static void interp_trunc_par(SSS_MAT *P, double eps)
+static void interp_trunc_par(SSS_MAT *P, double eps, int pmax)
 {
     const int n = P->num_rows;
     int *nrp = (int *)SSS_calloc((size_t)n + 1, sizeof(int));
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for schedule(dynamic, 1024)
     for (int i = 0; i < n; ++i) {
         const int lo = P->row_ptr[i], hi = P->row_ptr[i + 1];
         double pos_max = 0, neg_min = 0;
@@ -1031,16 +1086,18 @@ static void interp_trunc_par(SSS_MAT *P, double eps)
         pos_max *= eps;
         neg_min *= eps;
         for (int k = lo; k < hi; ++k) c += (P->val[k] >= pos_max) || (P->val[k] <= neg_min);
-        nrp[i + 1] = c;
+        nrp[i + 1] = (pmax > 0 && c > pmax) ? pmax : c;
     }
     for (int i = 0; i < n; ++i) nrp[i + 1] += nrp[i];
     const int kept = nrp[n];
     int *nci = (int *)SSS_calloc((size_t)(kept > 0 ? kept : 1), sizeof(int));
     double *nv = (double *)SSS_calloc((size_t)(kept > 0 ? kept : 1), sizeof(double));
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for schedule(dynamic, 1024)
     for (int i = 0; i < n; ++i) {
         const int lo = P->row_ptr[i], hi = P->row_ptr[i + 1];
         double pos_max = 0, neg_min = 0, pos_sum = 0, neg_sum = 0, pos_kept = 0, neg_kept = 0;
+        double pos_fac, neg_fac, cut_a = 0.0;
+        int cut_k = -1;
         for (int k = lo; k < hi; ++k) {
             double v = P->val[k];
             if (v > 0) { pos_sum += v; pos_max = SSS_max(pos_max, v); }
@@ -1048,19 +1105,27 @@ static void interp_trunc_par(SSS_MAT *P, double eps)
         }
         pos_max *= eps;
         neg_min *= eps;
+        const int capped = trunc_cut(P->val, lo, hi, pos_max, neg_min, pmax, &cut_a, &cut_k);
         int o = nrp[i];
-        for (int k = lo; k < hi; ++k) {
+        const int end = nrp[i + 1];
+        for (int k = lo; k < hi && o < end; ++k) {
             double v = P->val[k];
-            if (v >= pos_max) { nci[o++] = P->col_idx[k]; pos_kept += v; }
-            else if (v <= neg_min) { nci[o++] = P->col_idx[k]; neg_kept += v; }
+            if (!TRUNC_KEPT(v, k)) continue;
+            nci[o++] = P->col_idx[k];
+            if (v >= pos_max) pos_kept += v;
+            else neg_kept += v;
         }
-        const double pos_fac = pos_kept > SMALLFLOAT ? pos_sum / pos_kept : 1.0;
-        const double neg_fac = neg_kept < -SMALLFLOAT ? neg_sum / neg_kept : 1.0;
+        if (capped) {
+            trunc_capped_factors(pos_sum, neg_sum, pos_kept, neg_kept, &pos_fac, &neg_fac);
+        } else {
+            pos_fac = pos_kept > SMALLFLOAT ? pos_sum / pos_kept : 1.0;
+            neg_fac = neg_kept < -SMALLFLOAT ? neg_sum / neg_kept : 1.0;
+        }
         o = nrp[i];
-        for (int k = lo; k < hi; ++k) {
+        for (int k = lo; k < hi && o < end; ++k) {
             double v = P->val[k];
-            if (v >= pos_max) nv[o++] = v * pos_fac;
-            else if (v <= neg_min) nv[o++] = v * neg_fac;
+            if (!TRUNC_KEPT(v, k)) continue;
+            nv[o++] = v >= pos_max ? v * pos_fac : v * neg_fac;
         }
     }
     free(P->row_ptr);
@@ -1072,18 +1137,47 @@ static void interp_trunc_par(SSS_MAT *P, double eps)
     P->num_nnzs = kept;
 }
 
+/* 0 when P is a CSR matrix the truncation can walk: monotone row pointers from 0, arrays where there
+ * are entries (include/sss_hip.h sss_interp_trunc_host). */
+static int trunc_check(const SSS_MAT *P, int pmax)
+{
+    if (pmax < 0 || !P || P->num_rows <= 0 || !P->row_ptr || P->row_ptr[0] != 0) return ERROR_INPUT_PAR;
+    for (int i = 0; i < P->num_rows; ++i)
+        if (P->row_ptr[i + 1] < P->row_ptr[i]) return ERROR_INPUT_PAR;
+    const int nnz = P->row_ptr[P->num_rows];
+    if (nnz != P->num_nnzs || (nnz > 0 && (!P->col_idx || !P->val))) return ERROR_INPUT_PAR;
+    return 0;
+}
+
+int sss_interp_trunc_host(SSS_MAT *P, double eps, int pmax)
+{
+    const int rc = trunc_check(P, pmax);
+    if (rc) return rc;
+    interp_trunc_par(P, eps, pmax);
+    return 0;
+}
+
 void SSS_amg_interp_trunc(SSS_MAT *P, SSS_AMG_PARS *pars)
 {
     const double eps = pars->trunc_threshold;
+    const int pmax = sss_setup_pmax();
     int kept = 0, wcol = 0, wval = 0;
     if (P->num_nnzs >= (1 << 20)) {
-        interp_trunc_par(P, eps);
+        /* one timing line of its own, only when SSS_SETUP_PMAX is set (0: the uncapped truncation) */
+        const int timing = getenv("SSS_SETUP_TIMING") && getenv("SSS_SETUP_PMAX");
+        const int before = P->num_nnzs;
+        const double t0 = SSS_get_time();
+        interp_trunc_par(P, eps, pmax);
+        if (timing)
+            fprintf(stderr, "[setup]   truncation: host, cap %d, %d rows, %d of %d entries kept, %.4f s\n", pmax, P->num_rows,
+                    P->num_nnzs, before, SSS_get_time() - t0);
         return;
     }
     for (int i = 0; i < P->num_rows; ++i) {
         const int lo = P->row_ptr[i], hi = P->row_ptr[i + 1];
         double pos_max = 0, neg_min = 0, pos_sum = 0, neg_sum = 0, pos_kept = 0, neg_kept = 0;
-        double pos_fac, neg_fac;
+        double pos_fac, neg_fac, cut_a = 0.0;
+        int cut_k = -1;
         P->row_ptr[i] = kept;
         for (int k = lo; k < hi; ++k) {
             double v = P->val[k];
@@ -1092,23 +1186,33 @@ void SSS_amg_interp_trunc(SSS_MAT *P, SSS_AMG_PARS *pars)
         }
         pos_max *= eps;
         neg_min *= eps;
+        /* the cut is found before the row is compacted in place (the writes below stay behind the reads) */
+        const int capped = trunc_cut(P->val, lo, hi, pos_max, neg_min, pmax, &cut_a, &cut_k);
         for (int k = lo; k < hi; ++k) {
             double v = P->val[k];
-            if (v >= pos_max) { kept++; P->col_idx[wcol++] = P->col_idx[k]; pos_kept += v; }
-            else if (v <= neg_min) { kept++; P->col_idx[wcol++] = P->col_idx[k]; neg_kept += v; }
+            if (!TRUNC_KEPT(v, k)) continue;
+            kept++;
+            P->col_idx[wcol++] = P->col_idx[k];
+            if (v >= pos_max) pos_kept += v;
+            else neg_kept += v;
         }
-        pos_fac = pos_kept > SMALLFLOAT ? pos_sum / pos_kept : 1.0;
-        neg_fac = neg_kept < -SMALLFLOAT ? neg_sum / neg_kept : 1.0;
+        if (capped) {
+            trunc_capped_factors(pos_sum, neg_sum, pos_kept, neg_kept, &pos_fac, &neg_fac);
+        } else {
+            pos_fac = pos_kept > SMALLFLOAT ? pos_sum / pos_kept : 1.0;
+            neg_fac = neg_kept < -SMALLFLOAT ? neg_sum / neg_kept : 1.0;
+        }
         for (int k = lo; k < hi; ++k) {
             double v = P->val[k];
-            if (v >= pos_max) P->val[wval++] = v * pos_fac;
-            else if (v <= neg_min) P->val[wval++] = v * neg_fac;
+            if (!TRUNC_KEPT(v, k)) continue;
+            P->val[wval++] = v >= pos_max ? v * pos_fac : v * neg_fac;
         }
     }
     P->num_nnzs = P->row_ptr[P->num_rows] = kept;
     P->col_idx = (int *)SSS_realloc(P->col_idx, (size_t)kept * sizeof(int));
     P->val = (double *)SSS_realloc(P->val, (size_t)kept * sizeof(double));
 }
+#undef TRUNC_KEPT
 
 /*
  * Setup/SSS_inter.cu:400-547.  `aii` is carried from row to row exactly as the host twin

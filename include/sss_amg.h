@@ -277,6 +277,9 @@ void SSS_amg_complexity_print(SSS_AMG *mg);
 void SSS_amg_setup(SSS_AMG *mg, SSS_MAT *A, SSS_AMG_PARS *pars);
 int SSS_amg_coarsen(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars);
 void SSS_amg_interp(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_IMAT *S, SSS_AMG_PARS *pars);
+/* The relative rule at pars->trunc_threshold, per sign; with SSS_SETUP_PMAX=<n> in the environment
+ * (an engine extension, off by default; include/sss_hip.h sss_setup_pmax) also at most n
+ * entries per row. */
 void SSS_amg_interp_trunc(SSS_MAT *P, SSS_AMG_PARS *pars);
 void interp_DIR(SSS_MAT *A, SSS_IVEC *vertices, SSS_MAT *P, SSS_AMG_PARS *pars);
 

@@ -231,6 +231,34 @@ int sss_interp_mpass_host(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, 
  * and runs the host form on any error code.  With SSS_SETUP_TIMING one stderr line. */
 int sss_hip_interp_mpass(const SSS_MAT *A, const SSS_IMAT *S, const int *mark, SSS_MAT *P, double trunc_threshold,
                          int *passes);
+/* The cap on the entries per row of P, an engine extension that is off by default:
+ * SSS_SETUP_PMAX=<n> in the environment, n > 0; anything else (unset, not a number, <= 0) is 0 = off.
+ * SSS_AMG_PARS keeps the reference's layout, so the value cannot live there.  SSS_amg_interp_trunc,
+ * sss_interp_mpass_host and the device interpolations (sss_hip_interp_std, sss_hip_interp_exti,
+ * sss_hip_interp_mpass) read it through this helper. */
+int sss_setup_pmax(void);
+/* The truncation of an interpolation matrix P (columns already in coarse numbering) with the cap, on
+ * the host: OpenMP, row-parallel (count, prefix, fill).  Per row, in stored order: pos_sum, neg_sum,
+ * pos_max, neg_min; the survivors are the entries with v >= pos_max * eps || v <= neg_min * eps.  A row
+ * with at most pmax survivors (every row when pmax == 0) is SSS_amg_interp_trunc's row, bit for bit.
+ * Otherwise the pmax survivors of largest |v| are kept (ties: the earlier stored position), in stored
+ * order; pos_kept and neg_kept are their sums in stored order (v >= the positive threshold is the
+ * positive class, as in the uncapped branch order) and the factors follow the SMALLFLOAT rule, but for
+ * a class the cap removed entirely (pos_sum > 0 and pos_kept not above SMALLFLOAT, or the mirror case):
+ * when the other class was kept beyond SMALLFLOAT its factor is (pos_sum + neg_sum) / its kept sum, so
+ * the row sum of P survives.  P's arrays are freed and replaced on success.  Returns 0, or
+ * ERROR_INPUT_PAR (pmax < 0, a NULL or misshapen P) with P untouched. */
+int sss_interp_trunc_host(SSS_MAT *P, double eps, int pmax);
+/* The same on the GPU, bit for bit the host's arrays: upload, count, prefix, fill, download.  pmax == 0
+ * runs the one-lane-per-row kernels of the uncapped truncation.  pmax > 0 gives a row G lanes (1, 4, 16
+ * or 64, from the mean row length of P; SSS_HIP_INTERP_LANES forces it): the sums that depend on order
+ * are made in stored order by every lane of the group from the same loads, the cut of a capped row is
+ * found in pmax rounds, each a group-wide arg-max (by shuffles) of the key (|v|, then the smaller
+ * position) over the survivors strictly below the previous round's pick; no per-entry state, no local
+ * array.  Returns 0, or an error code with P untouched: ERROR_INPUT_PAR (as the host form, before the
+ * first HIP call), ERROR_MAT_SIZE (too many rows for the grid), ERROR_MISC (no device, a failed HIP
+ * call or copy). */
+int sss_hip_interp_trunc(SSS_MAT *P, double eps, int pmax);
 
 /* Progress hook of the setup (amg_amd/host/sss_setup.c): hook(ctx, mg, done, 0) once levels
  * 0 .. done-1 are final and none of them is the coarsest; hook(ctx, mg, num_levels - 1, 1) at

@@ -101,14 +101,18 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=5, help="alternated timing samples per hierarchy (at least 3)")
     ap.add_argument("--iters", type=int, default=10, help="iterations per time_iterations call")
     ap.add_argument("--skip-steps", action="store_true", help="skip the forced host / device setups")
+    ap.add_argument("--pmax", type=int, default=None,
+                    help="cap on the entries per row of P (sets SSS_SETUP_PMAX; DESIGN.md 6.9)")
     ap.add_argument("--out", type=Path, default=None)
     args = ap.parse_args()
     if A.device_count() < 1:
         print("no HIP device visible", file=sys.stderr)
         return 1
     os.environ["SSS_SETUP_TIMING"] = "1"
+    if args.pmax is not None:
+        os.environ["SSS_SETUP_PMAX"] = str(args.pmax)
     n = args.n ** 3
-    res = {"problem": f"{args.kind}-pt {args.n}^3", "rows": n, "mode": "hybrid/direct", "tol": args.tol,
+    res = {"problem": f"{args.kind}-pt {args.n}^3", "rows": n, "pmax": A.setup_pmax(), "mode": "hybrid/direct", "tol": args.tol,
            "host_threads": int(os.environ.get("OMP_NUM_THREADS", os.cpu_count())), "steps": {}, "variants": {}}
     M = A.generate(args.kind, args.n)   # stays alive: level 0 of every hierarchy copies it
 

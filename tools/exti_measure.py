@@ -14,6 +14,10 @@
     and the isolated rows; and the V-cycle loop on the same hierarchy in parity mode (exact GS-CF, Krylov
     coarse solve), at most --parity-cycles cycles.
 
+--pmax N runs everything with the cap on the entries per row of P (SSS_SETUP_PMAX=N) and adds
+the truncation's own seconds on either side to the per-level records; --pmax 0 keeps the cap off and reports
+the uncapped truncation's seconds the same way.
+
 Writes one JSON document to --out and prints it.  Needs a GPU; there is no fallback.
 """
 from __future__ import annotations
@@ -38,20 +42,33 @@ VARIANTS = {"pmis_interp2": 2, "pmis_interp3": 3}
 DEV = re.compile(r"(standard|extended\+i) P: device weights, (\d+) rows, (\d+) entries, (\d+) lanes per row, "
                  r"(\d+) rows on global tables, copies ([0-9.]+) s, kernels ([0-9.]+) s")
 HOST = re.compile(r"(standard|extended\+i) P: host weights ([0-9.]+) s, (\d+) rows, (\d+) entries")
+# the truncation's own seconds, printed when SSS_SETUP_PMAX is set (--pmax): a note at the end of
+# the device line, a line of its own before the host line (row-parallel form only: P of 2^20 entries or more)
+DEV_TRUNC = re.compile(r", (?:cap (\d+) at (\d+) lanes per row|no cap), truncation ([0-9.]+) s")
+HOST_TRUNC = re.compile(r"truncation: host, cap (\d+), (\d+) rows, (\d+) of (\d+) entries kept, ([0-9.]+) s")
 
 
 def weight_lines(text: str) -> list:
     """One record per level from the weights' timing lines of one setup."""
     out = []
+    host_trunc = None
     for line in text.splitlines():
         m = DEV.search(line)
         if m:
             out.append({"where": "device", "rows": int(m.group(2)), "entries": int(m.group(3)), "lanes": int(m.group(4)),
                         "global_rows": int(m.group(5)), "copies_s": float(m.group(6)), "kernels_s": float(m.group(7)),
                         "seconds": float(m.group(6)) + float(m.group(7))})
+            t = DEV_TRUNC.search(line)
+            if t:
+                out[-1].update(trunc_lanes=int(t.group(2)) if t.group(2) else 1, trunc_s=float(t.group(3)))
+        m = HOST_TRUNC.search(line)
+        if m:
+            host_trunc = {"trunc_s": float(m.group(5)), "trunc_entries_before": int(m.group(4))}
         m = HOST.search(line)
         if m:
             out.append({"where": "host", "rows": int(m.group(3)), "entries": int(m.group(4)), "seconds": float(m.group(2))})
+            out[-1].update(host_trunc or {})
+            host_trunc = None
     return out
 
 
@@ -63,19 +80,26 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=5, help="alternated timing samples per hierarchy (at least 3)")
     ap.add_argument("--iters", type=int, default=10, help="iterations per time_iterations call")
     ap.add_argument("--parity-cycles", type=int, default=60, help="cap of the parity-mode V-cycle loop (0: skip it)")
+    ap.add_argument("--pmax", type=int, default=None,
+                    help="cap on the entries per row of P (sets SSS_SETUP_PMAX; DESIGN.md 6.9); 0: no cap, but the "
+                         "truncation's own seconds are reported as with a cap")
+    ap.add_argument("--no-forced", action="store_true", help="skip the setups forced to the device and to the host")
+    ap.add_argument("--no-solve", action="store_true", help="stop after the forced setups")
     ap.add_argument("--out", type=Path, default=None)
     args = ap.parse_args()
     if A.device_count() < 1:
         print("no HIP device visible", file=sys.stderr)
         return 1
     os.environ["SSS_SETUP_TIMING"] = "1"
+    if args.pmax is not None:
+        os.environ["SSS_SETUP_PMAX"] = str(args.pmax)
     n = args.n ** 3
-    res = {"problem": f"7-pt {args.n}^3", "rows": n, "split": "PMIS", "mode": "hybrid/direct", "tol": args.tol,
+    res = {"problem": f"7-pt {args.n}^3", "rows": n, "split": "PMIS", "pmax": A.setup_pmax(), "mode": "hybrid/direct", "tol": args.tol,
            "host_threads": int(os.environ.get("OMP_NUM_THREADS", os.cpu_count())), "weights_per_level": {}, "variants": {}}
     M = A.generate(7, args.n)   # stays alive: level 0 of every hierarchy copies it
 
     # the weights of every level, forced to the device and to the host
-    for name, interp in VARIANTS.items():
+    for name, interp in ({} if args.no_forced else VARIANTS).items():
         per, nnz = {}, None
         for where, env in (("device", {ENV[0]: "1", ENV[1]: "0"}), ("host", {ENV[0]: "0"})):
             with environment(**env):
@@ -94,7 +118,12 @@ def main() -> int:
             res["weights_per_level"][name].append({
                 "level": l, "rows": d["rows"], "nnz_A": nnz[l] if l < len(nnz) else None, "nnz_P": d["entries"],
                 "lanes": d["lanes"], "global_rows": d["global_rows"], "device_s": d["seconds"], "copies_s": d["copies_s"],
-                "kernels_s": d["kernels_s"], "host_s": h["seconds"]})
+                "kernels_s": d["kernels_s"], "host_s": h["seconds"], "trunc_lanes": d.get("trunc_lanes"),
+                "device_trunc_s": d.get("trunc_s"), "host_trunc_s": h.get("trunc_s"),
+                "nnz_P_before_truncation": h.get("trunc_entries_before")})
+
+    if args.no_solve:
+        return finish(res, args)
 
     # the two hierarchies in throughput mode
     b = np.random.default_rng(1).standard_normal(n)
@@ -121,7 +150,7 @@ def main() -> int:
             L = D.H.level(l)
             rp, _, val = A.csr_arrays(L.P, copy=False)
             cf = np.ctypeslib.as_array(L.cfmark.d, shape=(L.A.num_rows,))
-            v["p_per_level"].append({"level": l, "max_abs_p": float(np.abs(val).max()),
+            v["p_per_level"].append({"level": l, "max_abs_p": float(np.abs(val).max()), "longest_row": int(np.diff(rp).max()),
                                      "f_rows_without_pattern": int(((np.diff(rp) == 0) & (cf == 0)).sum()),
                                      "isolated_rows": int((cf == 2).sum())})
         print(f"[exti] {name}: setup {v['setup_s']:.2f} + mirror {v['mirror_after_s']:.2f} s, rows {v['rows']}, "
@@ -189,6 +218,10 @@ def main() -> int:
             print(f"[exti] {name}: parity mode {len(rel)} cycles, relres {rel[-1]:.3e}", file=sys.stderr, flush=True)
         D.H.close()
 
+    return finish(res, args)
+
+
+def finish(res, args) -> int:
     text = json.dumps(res, indent=1)
     if args.out:
         args.out.parent.mkdir(parents=True, exist_ok=True)
